@@ -3,6 +3,8 @@
 configs[1]: batch 16 per GPU, bf16 operands / f32 accumulate, synthetic inputs and filler weights).
 
     python bench.py --gpus N --steps K --warmup W        # N > 1: starts its own N ranks (see self_launch)
+    python bench.py --gpus 1 --steps K --warmup W --full # + the roofline, cpu_baseline and parity legs (below)
+    python bench.py ... --dump-outputs DIR               # + DIR/samples.npy: what the last timed step returned
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W           # or under a launcher that already set RANK / WORLD_SIZE
 
@@ -11,13 +13,15 @@ per timestep  UNet.encode -> sigma net -> UNet.forward -> scheduler update.  Eve
 own batches (weak scaling, independent samples); the finished samples stay in HBM and the
 single collective is one RCCL all-gather of them inside the timed region.  Rank 0 prints ONE JSON line.
 
-The timed region runs the product path with no instrumentation.  After it, rank 0 runs ONE more step with
-HIP events around every convolution launch (on the launch stream) for the `roofline` object:
+The timed region runs the product path with no instrumentation.  A plain run sets up, warms up, times the K steps,
+writes DIR/samples.npy when asked to, and prints the line.  With --full, rank 0 afterwards runs ONE more step with
+HIP events around every convolution launch (on the launch stream) for the `roofline` object, and the host legs:
   roofline     all nlc_conv2d launches of a step: algorithmic direct-conv FLOPs / their summed duration;
                peak = 2.5 PFLOP/s dense bf16 (MI355X_MICROARCH.md).  `traffic` comes from separate rocprofv3
                --pmc passes of the same build (profiles/, tagged with the hash of the kernel sources).
   cpu_baseline the CPU oracle (oracle/, a port of the reference's PyTorch-CPU path) timed on the host
-               cores of this box on a bounded sample of the same workload, extrapolated.
+               cores of this box on a bounded sample of the same workload, extrapolated; with it `parity`, the HIP
+               path against the oracle on the same seeded image.
 
 Other workloads (BASELINE.json configs[2], configs[3]; not the headline metric):  --config edm32 | celebahq256.
 """
@@ -497,8 +501,14 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=sorted(PRECISIONS),
                     help="bf16 (BASELINE.json configs[1]) | f16 (the reference's own use_fp16 mode) | f32 (exact f32 MFMA) | "
                          "f32x3 (f32 storage, split-f16 three-pass matrix math: the 1e-3-parity path)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs the headline figure does not need: the instrumented roofline step, "
+                         "the CPU baselines and the parity comparison with the CPU oracle (off by default)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the cpu_baseline / parity legs")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: leave out the instrumented roofline step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned (the finished samples of every rank, "
+                         "float32 / float64) to DIR/samples.npy; at most 64 MB (a fixed seeded choice of images beyond that)")
     ap.add_argument("--graph", action="store_true", help="replay each network evaluation from a captured hipGraph")
     ap.add_argument("--ops-flag", action="append", default=[], metavar="NAME=VALUE", help="A/B: set a module-level switch of diffusion_nlc_amd.ops")
     ap.add_argument("--gn-fusion", action="store_true", help="A/B: GroupNorm in the 3x3 convs' LDS prologue instead of a separate pass")
@@ -586,6 +596,8 @@ def main():
     elapsed = float(t.item())
     per_rank = per_rank.cpu()
     assert gathered.shape[0] == args.steps * world and torch.isfinite(gathered).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), gathered[args.steps * world - world:])
 
     images = wl.batch * args.steps * world
     line = {
@@ -606,9 +618,9 @@ def main():
     if rank == 0:
         if not args.dry_run and wl.gflop_per_image:
             line["end_to_end_tflops_per_gpu"] = (images / world) * wl.gflop_per_image / 1e3 / elapsed
-        if not args.dry_run and not args.no_roofline:
+        if args.full and not args.dry_run and not args.no_roofline:
             line["roofline"] = roofline_leg(wl, xs[0], dtype, args, line["ms_per_step"])
-        if not args.dry_run and not args.no_cpu_baseline and not args.tiny and world == 1:
+        if args.full and not args.dry_run and not args.no_cpu_baseline and not args.tiny and world == 1:
             line["cpu_baseline"] = wl.cpu_baseline()
             if wl.name == "adm256":
                 line["cpu_baseline"]["configs0_unet_simple_32"] = cfg0_baseline(device)
@@ -620,6 +632,24 @@ def main():
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(folder, last):
+    """--dump-outputs: `last` = the finished samples of the last timed step, [world, B, ...] in global batch order (what the
+    caller of the timed path holds after the gather) -> folder/samples.npy, [world * B, ...] in float32 (float64 when the
+    path returns float64).  Beyond DUMP_LIMIT_BYTES a fixed seeded choice of the images, in ascending order, is kept."""
+    x = last.reshape((-1,) + tuple(last.shape[2:]))
+    x = x.to(torch.float64 if x.dtype == torch.float64 else torch.float32).cpu()
+    keep = DUMP_LIMIT_BYTES // max(1, x[0].numel() * x.element_size())
+    if x.shape[0] > keep:
+        idx = torch.randperm(x.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        x = x.index_select(0, idx)
+    import numpy as np
+    folder.mkdir(parents=True, exist_ok=True)
+    np.save(folder / "samples.npy", x.contiguous().numpy())
 
 
 def roofline_leg(wl, x, dtype, args, ms_per_step):

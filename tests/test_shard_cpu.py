@@ -95,6 +95,34 @@ def test_bench_self_launches_its_ranks_under_gloo():
     assert bad.returncode != 0            # no GPU here and no --dry-run: every rank refuses
 
 
+def test_bench_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """`--dump-outputs DIR`: DIR/samples.npy holds what the LAST timed step returned, in float32, and the inputs are the seeded
+    host draws.  Under --dry-run a step returns x * 0.5, so with --warmup 1 --steps 2 the file is half the third draw of the
+    workload's generator (seed 1234), exactly.  A plain run carries none of the --full legs."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+    import numpy as np
+    root = Path(__file__).resolve().parent.parent
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env["NLC_BENCH_FORCE_CPU"] = "1"
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--dry-run", "--tiny",
+                        "--batch", "2", "--dump-outputs", str(tmp_path / "out")], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert not {"roofline", "cpu_baseline", "parity"} & set(line)
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == ["samples.npy"]
+    got = np.load(tmp_path / "out" / "samples.npy")
+    g = torch.Generator().manual_seed(1234)
+    draws = [torch.randn((2, 3, 64, 64), generator=g) for _ in range(3)]
+    assert got.dtype == np.float32 and got.shape == (2, 3, 64, 64)
+    assert np.array_equal(got, (draws[2] * 0.5).numpy())
+
+
 # ---- the reference's own entry points, sharded: image_sample.evaluate_unconstraint and EDMImageExperiment.evaluate_edm -----------------
 # The HIP path has no CPU fallback, so a stand-in experiment supplies the per-batch sampler; everything else - batch ownership, replay
 # of the single host generator for batches another rank owns, the once-only skip-if-exists decision, the all-gather, rank 0 writing the

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Fold rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes (two separate runs of the same command, CSV output) into the HBM-traffic
-JSON that bench.py attaches to its `roofline` object.
+JSON that bench.py --full attaches to its `roofline` object.
 
     python tools/pmc_traffic.py <step_fetch.csv> <step_write.csv> <dominant_fetch.csv> <dominant_write.csv> <nlc_steps> > profiles/rNN_pmc_traffic.json
 
