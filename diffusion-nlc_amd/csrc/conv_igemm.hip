@@ -332,6 +332,8 @@ extern "C" int nlc_conv2d_stats_partials(const nlc_conv_desc* d, int dtype) {
     if (!desc_sane(d, dtype)) return 0;
     KParams p{};
     fill_params(d, p);
+    // (the small-map kernel is asked first, as in nlc_conv2d and nlc_conv2d_workspace_bytes: it adds totals to whole 128-channel tiles)
+    { SmallGeom sg; if (small_wanted(d, p, dtype, sg)) return p.Cout % BN == 0 ? 1 : 0; }
     if (nlc_conv_narrow_ok(p, dtype)) return 0;          // the <= 16-channel kernel emits none
     const int P = nlc_conv_halo_stats_partials(p, dtype);
     if (P > 0) return P;
