@@ -46,12 +46,13 @@ __global__ __launch_bounds__(RT) void row_sumsq_kernel(const float* __restrict__
     if (threadIdx.x == 0) sumsq[blockIdx.x] = tot;
 }
 
-// first index i with table[i] >= v  (torch.searchsorted, right=False), n if none
+// first index i with table[i] >= v  (torch.searchsorted, right=False), n if none.  A NaN v compares as larger than every entry,
+// as in ATen's search (its test is !(mid >= v) too): n
 __device__ __forceinline__ int lower_bound(const float* __restrict__ table, int n, float v) {
     int lo = 0, hi = n;
     while (lo < hi) {
         const int mid = (lo + hi) >> 1;
-        if (table[mid] < v) lo = mid + 1; else hi = mid;
+        if (!(table[mid] >= v)) lo = mid + 1; else hi = mid;
     }
     return lo;
 }

@@ -369,7 +369,12 @@ int nlc_refine_sigma(const float* sumsq, float sqrt_dim, float norm_max, float n
  *                       else [n_sigmas-1] f32 slopes 1/(eps+sigmas[i+1]-sigmas[i]) -> continuous t by linear
  *                       interpolation, t = i + slopes[i]*(sigma - sigmas[i]), i = clamp(searchsorted-1, 0, n-2)
  *                       (sigma_to_t_interp, src/schedulers.py:210-220; src/torchinterp1d.py:10-154).
- *   time_shift        : subtracted from every t when refine and min_b t > 0 (src/experiments.py:411-412). */
+ *   time_shift        : subtracted from every t when refine and min_b t > 0 (src/experiments.py:411-412).
+ * Non-finite sigmas (the lookup of nlc_refine_sigma*, nlc_sigma_correct and nlc_proj_sigma alike): searchsorted treats a NaN
+ * sigma as larger than every table entry, as torch.searchsorted does, so the discrete lookup returns n_sigmas (+inf does too,
+ * -inf returns 0); the continuous lookup then interpolates from i = n_sigmas-2 and returns NaN (+-inf for +-inf).  The
+ * [0, 1000] clamp of nlc_refine_sigma* / nlc_sigma_correct is fminf(fmaxf(t, 0), 1000), which turns a NaN t into 0 where
+ * torch.clamp would keep it; sigma_t itself stays NaN, so the sample is lost either way.  nlc_proj_sigma does not clamp. */
 typedef struct nlc_sigma_desc {
     const float* sumsq;      /* [B] row sums of squares of xt (refine only) */
     const float* sigma_in;   /* [B] or NULL */

@@ -342,3 +342,185 @@ def test_inline_asm_loads_are_never_touched_in_flight(tmp_path):
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-4000:]
     assert "0 touches" in r.stdout
+
+
+# ---- the references of tests/test_sampler_ops_gpu.py (tests/sampler_refs.py) held to the CPU oracle, bit for bit in f32, and the
+#      preconditions its GPU cases rely on
+def _oracle_schedule(continuous_t):
+    from oracle import sched as osch
+    return osch.get_sampler("ddim", 1000, 50, sigma_style="DDIM", start_sigma=100, end_sigma=0, continuous_t=continuous_t)
+
+
+@pytest.mark.parametrize("continuous_t", [False, True], ids=["discrete", "continuous"])
+def test_sampler_refs_lookup_equals_the_oracle(continuous_t):
+    from tests import sampler_refs as R
+    S = _oracle_schedule(continuous_t)
+    sigmas, slopes = R.tables()["cont" if continuous_t else "t1000"]
+    assert torch.equal(S.sigmas, sigmas) and (slopes is not None) == continuous_t
+    g = R.gen(("lookup", continuous_t))
+    v = torch.cat([torch.exp(torch.rand(4000, generator=g) * 13 - 7), sigmas, sigmas * 0.5, sigmas * 1.5,
+                   torch.tensor([0.0, -1.0, 1e-30, 1e30])]).float()
+    assert torch.equal(R.lookup_f32(sigmas, slopes, v), S.get_t_from_sigma(v).float())
+    for kind, (tab, sl) in R.tables().items():
+        assert bool((tab[1:] > tab[:-1]).all()) and tab.dtype == torch.float32, kind
+        assert tab.numel() == {"t51": 51, "t1000": 1000, "t1001": 1001, "cont": 1000}[kind]
+    # a NaN sigma: n, as torch.searchsorted finds it (include/nlc_hip.h documents the kernels' lookup the same way)
+    assert R.lookup_f32(sigmas, None, torch.tensor([float("nan")])).item() == sigmas.numel()
+
+
+def _oracle_denoise(S, xt, t, sigma_t, sigma_prev, style, refine, time_shift=0, norm_min=None, norm_max=None, r=None):
+    """oracle/loop.py get_denoise_vector with stand-in networks -> (sigma_t, sigma_prev, the t the eps network was given)."""
+    from oracle.loop import DiffusionOracle
+    seen = {}
+
+    def eps_fn(z, tt):
+        seen["t"] = tt.clone()
+        return torch.zeros_like(z)
+    O = DiffusionOracle(eps_fn, lambda z, tt: z, lambda f: r, S, data_shape=xt.shape[1:], learn_epsvar=False,
+                        norm_min=norm_min, norm_max=norm_max, time_shift=time_shift)
+    _, _, st, sp = O.get_denoise_vector(xt, t, sigma_t, sigma_prev, style=style, refine_prior_sigma=refine)
+    return st, sp, seen["t"].float().reshape(-1)
+
+
+@pytest.mark.parametrize("continuous_t", [False, True], ids=["discrete", "continuous"])
+def test_sampler_refs_refine_clamp_and_shift_equal_the_oracle(continuous_t):
+    """oracle/loop.py:80-90.  The state is [v, 0, 0] with a 12-bit v, so that its norm is v exactly and the sum of squares the
+    kernels are given is v*v exactly."""
+    import math
+    from tests import sampler_refs as R
+    S = _oracle_schedule(continuous_t)
+    sigmas, slopes = R.tables()["cont" if continuous_t else "t1000"]
+    g = R.gen(("refine-oracle", continuous_t))
+    B, dim, nmin, nmax = 600, 3, 0.05, 2.0
+    v = torch.randint(1, 4096, (B,), generator=g).float() / 16.0 * 2.0 ** -torch.randint(0, 12, (B,), generator=g).float()
+    raw = torch.exp(torch.rand(B, generator=g) * 10.6 - 5.3).float()
+    scal = (math.sqrt(dim), nmax / math.sqrt(dim), nmin / math.sqrt(dim))
+    sg = R.refine_clamp_f32(v * v, raw, *scal)
+    assert bool((sg > raw).any()) and bool((sg < raw).any()) and bool((sg == raw).any())      # both clamps bind, and neither
+    t_all = R.lookup_f32(sigmas, slopes, sg)
+    pos = torch.nonzero(t_all > 0).reshape(-1)
+    zero = torch.nonzero(t_all <= 0).reshape(-1)
+    assert pos.numel() > 100 and zero.numel() > 0
+    for idx, shifted in ((pos, True), (torch.cat([pos[:200], zero[:1], pos[200:]]), False)):
+        xt = torch.zeros(idx.numel(), dim)
+        xt[:, 0] = v[idx]
+        st, sp, t = _oracle_denoise(S, xt, torch.tensor(0), raw[idx].view(-1, 1), torch.tensor(0.8), "base", True, time_shift=3,
+                                    norm_min=nmin, norm_max=nmax)
+        assert torch.equal(st.reshape(-1), sg[idx])
+        want = R.shift_clamp_f32(t_all[idx], 3)
+        assert torch.equal(t, want)
+        assert torch.equal(want, (t_all[idx] - 3).clamp(0, 1000) if shifted else t_all[idx].clamp(0, 1000))
+        # (3 + 1) half ulps of the largest intermediate bound the f32 chain against its f64 evaluation (the bound the GPU test uses)
+        ref, norm_x = R.refine_clamp_f64((v * v)[idx], raw[idx], *scal)
+        assert bool(((st.reshape(-1).double() - ref).abs() <= 4 * R.U32 * torch.maximum(norm_x, ref).clamp(min=scal[1])).all())
+
+
+@pytest.mark.parametrize("style", ["pred", "pred_partial"])
+@pytest.mark.parametrize("continuous_t", [False, True], ids=["discrete", "continuous"])
+def test_sampler_refs_correct_step_equals_the_oracle(continuous_t, style):
+    """oracle/loop.py:94-99."""
+    from tests import sampler_refs as R
+    S = _oracle_schedule(continuous_t)
+    sigmas, slopes = R.tables()["cont" if continuous_t else "t1000"]
+    g = R.gen(("correct-oracle", continuous_t))
+    B = 500
+    st0 = torch.rand(B, generator=g) * 40 + 0.05
+    st0[::5] = sigmas[torch.randint(1, 1000, (B // 5,), generator=g)]
+    sp0 = st0 * 0.8
+    r = torch.randn(B, generator=g) * 0.5
+    r[::5] = 0.0
+    r[1::50] = -1.5
+    r[2::50] = 1e4
+    st, sp, t = _oracle_denoise(S, torch.zeros(B, 3), torch.zeros(B, dtype=torch.long), st0.view(-1, 1), sp0.view(-1, 1), style, False,
+                                r=r.view(-1, 1))
+    dist_hat, dist_prev = R.correct_f32(st0, sp0, r)
+    assert torch.equal(st.reshape(-1), dist_hat)
+    assert torch.equal(sp.reshape(-1), dist_prev if style == "pred" else sp0)
+    assert torch.equal(t, R.lookup_f32(sigmas, slopes, dist_hat).clamp(0.0, 1000.0))
+    assert torch.equal(dist_hat[::5], st0[::5])                                      # r = 0 lands on the table entry itself
+    ref = R.c_in_f64(dist_hat)
+    c_in = (1.0 / (dist_hat * dist_hat + 1.0)).sqrt()
+    assert bool(((c_in.double() - ref).abs() <= 5 * R.U32 * ref).all())
+
+
+@pytest.mark.parametrize("sigma_data", [0.5, 1.0])
+def test_sampler_refs_edm_scalars_equal_the_oracle(sigma_data):
+    """oracle/loop.py EdmOracle.encode_edm / pred_edm: the stand-in network records c_in * 1 and c_noise; F = 0 leaves c_skip,
+    x = 0 leaves c_out."""
+    from oracle.loop import EdmOracle
+    from tests import sampler_refs as R
+    B = 257
+    sigma = R.edm_sigmas(B, sigma_data)
+    assert sigma[-1].item() == sigma_data and bool((sigma[:-1].float().double() != sigma[:-1]).all())
+    seen = {}
+
+    def net(x, c_noise):
+        seen["x"], seen["c_noise"] = x, c_noise
+        return seen["F"]
+    O = EdmOracle(net, net, None, data_shape=(1, 1, 1), sigma_data=sigma_data)
+    c_in, c_noise, c_skip, c_out = R.edm_scalars_f32(sigma, sigma_data)
+    seen["F"] = torch.zeros(B, 1, 1, 1)
+    assert torch.equal(O.pred_edm(torch.ones(B, 1, 1, 1, dtype=torch.float64), sigma).reshape(-1), c_skip)
+    assert torch.equal(seen["x"].reshape(-1), c_in) and torch.equal(seen["c_noise"], c_noise)
+    seen["F"] = torch.ones(B, 1, 1, 1)
+    assert torch.equal(O.pred_edm(torch.zeros(B, 1, 1, 1, dtype=torch.float64), sigma).reshape(-1), c_out)
+    O.encode_edm(torch.ones(B, 1, 1, 1, dtype=torch.float64), sigma)
+    assert torch.equal(seen["x"].reshape(-1), c_in) and torch.equal(seen["c_noise"], c_noise)
+    r_in, _, r_skip, r_out = R.edm_scalars_f64(sigma, sigma_data)                   # the half-ulp counts of the GPU test
+    for got, ref, n in ((c_skip, r_skip, 5), (c_out, r_out, 7), (c_in, r_in, 6)):
+        assert bool(((got.double() - ref).abs() <= n * R.U32 * ref).all())
+
+
+def test_sampler_refs_preconditions_of_the_gpu_cases():
+    import math
+    from fractions import Fraction
+    from tests import sampler_refs as R
+    for kind, (sigmas, slopes) in R.tables().items():
+        # raw sigmas meant to be table entries are bit-equal to one
+        sumsq, raw = R.refine_inputs(sigmas, 2500, kind)
+        ties = raw[3::6].contiguous()
+        assert torch.equal(sigmas[torch.searchsorted(sigmas, ties)], ties)
+        sg = R.refine_clamp_f32(sumsq, raw, *R.REFINE_SCALARS)
+        assert torch.equal(sg[3::6], ties) and torch.equal(sg[0::6], raw[0::6])                     # neither clamp binds
+        assert bool((sg[1::6] > raw[1::6]).all()) and bool((sg[2::6] < raw[2::6]).all())            # lower / upper clamp binds
+        assert bool((raw[4::6] > sigmas[-1]).all()) and bool((raw[5::6] <= sigmas[0]).all())
+        # the every-t-positive batch, and the same batch with one sample at t == 0
+        sumsq, raw = R.refine_inputs(sigmas, 2500, kind, every_t_positive=True)
+        t = R.lookup_f32(sigmas, slopes, R.refine_clamp_f32(sumsq, raw, *R.REFINE_SCALARS))
+        assert bool(t.min() > 0) and bool((t >= 3).any())
+        for z in (0, 70, 2499):
+            sumsq, raw = R.refine_inputs(sigmas, 2500, kind, every_t_positive=True, zero_at=z)
+            t = R.lookup_f32(sigmas, slopes, R.refine_clamp_f32(sumsq, raw, *R.REFINE_SCALARS))
+            assert t[z].item() == 0.0 and int((t <= 0).sum()) == 1
+    # cosine inputs: condition below 1e3 wherever the products do not vanish; the kernel's formula agrees with ATen inside the bound
+    for D in (1, 63, 1024, 1025, 3072, 196608):
+        a, b = R.cosine_rows(D)
+        scale, dot = R.cosine_parts(a, b)
+        for k in ("random", "identical", "opposite", "tiny"):
+            i = R.COS_KINDS.index(k)
+            assert scale[i] / dot[i] < 1e3, (D, k)
+        assert scale[3].item() == 0.0 and scale[4].item() == 0.0
+        assert a[5].norm().item() < R.COS_EPS and a[4].norm().item() == 0.0
+        na, nb = a.norm(dim=1, keepdim=True).clamp(min=R.COS_EPS), b.norm(dim=1, keepdim=True).clamp(min=R.COS_EPS)
+        ref = torch.nn.CosineSimilarity(dim=1, eps=R.COS_EPS)(a, b)
+        assert bool((((a / na) * (b / nb)).sum(1) - ref).abs().le((R.sumsq_chain_f64(D) + 1) * R.U64 * scale).all())
+    # the exact sum of squares, against rational arithmetic
+    x = torch.randn(37, generator=R.gen("exact"), dtype=torch.float64).numpy() * 1e3
+    exact = sum(Fraction(float(v)) ** 2 for v in x)
+    assert R.exact_sumsq(x) == float(exact)
+    # the propagated bound of proj_sigma holds for its f32 restatement
+    g = R.gen("proj-bound")
+    B, sd = 4000, math.sqrt(3072.0)
+    nm = 31.0 / sd
+    cn = torch.rand(B, generator=g) * 3 + 0.05
+    cn[::4] = nm * (1 + 0.01 * torch.randn(B // 4, generator=g))
+    args = (((cn * sd) ** 2).float(), cn * 1.1, torch.rand(B, generator=g) * 60 + 0.01, torch.rand(B, generator=g) * 50 + 0.01,
+            sd, nm, nm ** 2, 0.99, 1.25, 0.2, 0.3, 0.4)
+    ref, bound = R.proj_f64_with_bound(*args)
+    assert bool(((R.proj_f32(*args)[0].double() - ref).abs() <= bound).all())
+    assert bool((bound < 64 * R.U32 * ref.abs()).all())                                                  # and it is no blank cheque
+    # cast edge values survive the CPU conversion as the GPU test expects them
+    v = R.cast_values(1023).float()
+    assert v[0].item() == 1.0 and v[1].item() == 1.0 + 2.0 ** -22 and math.isinf(v[2].item()) and v[4].item() == 0.0
+    assert 0.0 < v[5].item() < 1.1754944e-38 and math.copysign(1.0, v[7].item()) == -1.0 and math.isnan(v[8].item())
+    assert v[11].item() == 0.0 and v[12].item() == 2.0 ** -148 and math.isinf(v[13].item())
