@@ -634,7 +634,7 @@ int launch_fast(const KParams& p, hipStream_t stream) {
 // Shapes of the fast path: 3x3 (any stride, any top/left padding: the far side is zero-filled by the tap tables, so
 // the stride-2 Downsample convs of ADM / the sigma nets and the asymmetric-pad ones of the simple UNet qualify) and
 // unpadded stride-1 1x1.
-static bool fast_shape(const KParams& p) {
+bool nlc_conv_fast_shape(const KParams& p) {
     const bool k3 = p.KH == 3 && p.KW == 3;
     const bool k1 = p.KH == 1 && p.KW == 1 && p.pad_t == 0 && p.pad_l == 0 && p.stride == 1;
     if (!(k3 || k1)) return false;
@@ -642,15 +642,14 @@ static bool fast_shape(const KParams& p) {
     return (int64_t)p.B * p.Hin * p.Win < (1ll << 31);
 }
 
-// Split-K policy (the caller opts in by passing a workspace; the f32 parity path never does): shapes with fewer output tiles than
-// 2 per CU and a long K; at least 2 channel blocks (18 / 2 k-steps) per split, at most 8 splits, aiming at >= 2
-// workgroups per CU (the 8x8 / 16x16 levels of ADM-256 at B = 16 have 64 / 256 tiles for 144-288 k-steps).
-int nlc_conv_fast_ksplit(const KParams& p, int dtype) {
-    if ((p.Cout & 3) || !fast_shape(p) || (p.tuning & 2048)) return 1;       // bit 11: no split-K anywhere (A/B, stress test)
+// Split-K of a launch that nlc_conv_fast_shape takes: the number of k-slices that brings its MT x NT tiles to `target` workgroups
+// (1 = none; the planner names the target): at least 2 channel blocks (18 / 2 k-steps) per split, at most 8 splits (the 8x8 / 16x16
+// levels of ADM-256 at B = 16 have 64 / 256 tiles for 144-288 k-steps).
+int nlc_conv_fast_ksplit(const KParams& p, int dtype, int target) {
+    if (p.Cout & 3) return 1;
     const bool k3 = p.KH == 3;
     const int tiles = p.MT * p.NT;
     const int ncb = p.Cin_pad / (nlc_is16(dtype) ? Mma<bf16_raw>::KBE : Mma<float>::KBE);
-    const int target = (p.tuning & 16384) ? 256 : 512;           // workgroups aimed at (A/B: bit 14 = one per CU)
     if (tiles >= target) return 1;
     int s = cdiv(target, tiles);
     // >= 18 (3x3) / 8 (1x1) k-steps per split; a 3x3 launch that would otherwise put fewer than 128 workgroups on the chip goes down to
@@ -662,21 +661,12 @@ int nlc_conv_fast_ksplit(const KParams& p, int dtype) {
     return s < 2 ? 1 : s;
 }
 
-// GroupNorm statistics ride along on the fast path when the N-tiles are whole and the output is 16-bit NHWC: per tile from the conv
-// epilogue if every 128-pixel tile lies inside one image, else (and from the last-arriving workgroup when K is split) per 16-pixel row
-int nlc_conv_fast_stats_partials(const KParams& p, int dtype) {
-    return (nlc_is16(dtype) && p.out_mode == NLC_OUT_NHWC && (p.Cout % BN) == 0 && fast_shape(p)) ? 1 : 0;
-}
-
-// workspace of a split launch: the arrival counters (4 KiB in front; tiles < 512) + ks x (whole 128 x 128 tiles) f32 partial sums
-int64_t nlc_conv_fast_split_bytes(const KParams& p, int ks) {
-    return ks > 1 ? (int64_t)ks * p.MT * p.NT * (BM * BN) * (int64_t)sizeof(float) + 4096 : 0;
-}
-
-// returns NLC_EUNSUPPORTED when the shape is not one the fast path handles (caller falls back)
-int nlc_conv_fast_dispatch(const KParams& p, int dtype, hipStream_t stream) {
-    if (!fast_shape(p)) return NLC_EUNSUPPORTED;
+// GroupNorm statistics (p.stats) ride along per tile from the conv epilogue if every 128-pixel tile lies inside one image, else (and
+// from the last-arriving workgroup when K is split: p.ksplit > 1, p.partial = the caller's workspace) per 16-pixel row
+int nlc_conv_fast_launch(const KParams& p, int dtype, hipStream_t stream) {
     const bool k3 = p.KH == 3;
+    NLC_REQUIRE((k3 ? p.KW == 3 : p.KH == 1 && p.KW == 1) && (p.ksplit == 1 || (p.partial && p.ksplit <= 8)),
+                "nlc_conv2d(fast): internal: planner/kernel disagreement");
     // deep pipeline for launches that leave every workgroup alone on its CU (tuning bit 12: never, bit 13: always - A/B)
     static DeviceOnce once;
     const int ncu = once.ncu[nlc_device_once(once, [] {})];

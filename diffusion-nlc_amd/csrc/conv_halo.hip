@@ -1137,77 +1137,39 @@ int launch_halo(const KParams& p, hipStream_t stream) {
 }  // namespace
 
 
-static bool halo_eligible(const KParams& p, int dtype, bool* forced_out) {
-    // per-call policy (nlc_conv_desc.policy): no process-wide switch, so the dispatch a test forces and the dispatch a
-    // benchmark measures are chosen by the caller, launch by launch
-    const bool forced = p.policy == NLC_CONV_FORCE_HALO;
-    if (forced_out) *forced_out = forced;
-    if (p.policy == NLC_CONV_NO_HALO || p.policy == NLC_CONV_GENERIC) return false;
+// Does the halo kernel take this launch, and how (conv_params.h): 3x3 / stride 1 / pad 1 (optionally on the nearest-2x upsampled
+// input), output H and W multiples of 16.  Whether it pays (tile counts, nlc_conv_desc.policy / tuning) is the planner's business.
+bool nlc_conv_halo_shape(const KParams& p, int dtype, HaloShape& h) {
     if (!(p.KH == 3 && p.KW == 3 && p.pad_t == 1 && p.pad_l == 1 && p.stride == 1)) return false;
     const int HL = p.ups ? 2 * p.Hin : p.Hin, WL = p.ups ? 2 * p.Win : p.Win;
     if (p.Hout % PATCH || p.Wout % PATCH || p.Hout != HL || p.Wout != WL) return false;
     const int kbe = nlc_is16(dtype) ? MmaH<bf16_raw>::KBE : MmaH<float>::KBE;
     if (p.C0 % kbe || p.C1 % kbe || p.Cin_pad / kbe > 128) return false;
     if ((int64_t)p.B * p.Hout * p.Wout >= (1ll << 31)) return false;
+    h.tiles = p.B * (p.Hout / PATCH) * (p.Wout / PATCH) * p.NT;
+    // SPLIT instantiation: 16-bit, whole N-tiles, no GroupNorm prologue; at most 4 slices of at least four 64-channel blocks (36
+    // k-steps) each: 256->1024 @16^2 at 2 per split lost 12 %
+    const int ncb = p.Cin_pad / kbe;
+    h.max_ksplit = (nlc_is16(dtype) && !p.gn_coef && (p.Cout % BN) == 0) ? (ncb / 4 < 4 ? ncb / 4 : 4) : 1;
+    h.prologue = dtype == NLC_BF16;                  // (GroupNorm prologue: bf16 instantiation only - it is off by default)
     return true;
 }
 
-static int halo_tiles(const KParams& p) { return p.B * (p.Hout / PATCH) * (p.Wout / PATCH) * p.NT; }
-
-// Split-K (SPLIT instantiation): launches with fewer tiles than CUs and at least four 64-channel blocks per
-// split - the 16x16 level of ADM-256 at B = 16 (1024->1024: 128 tiles x 2, 1024->512: 64 tiles x 4).  bf16, whole N-tiles, no
-// GroupNorm prologue; the caller opts in by passing the workspace (nlc_conv2d_workspace_bytes).  tuning bit 7 disables it (A/B).
-int nlc_conv_halo_ksplit(const KParams& p, int dtype) {
-    if (!nlc_is16(dtype) || p.gn_coef || (p.Cout % BN) != 0 || (p.tuning & (128 | 2048))) return 1;       // bit 11: no split-K anywhere (A/B, stress test)
-    if (!halo_eligible(p, dtype, nullptr)) return 1;
-    const int tiles = halo_tiles(p), ncb = p.Cin_pad / MmaH<bf16_raw>::KBE;
-    if (tiles >= 256) return 1;
-    int ks = 256 / tiles;
-    if (ks > 4) ks = 4;
-    if (ks > ncb / 4) ks = ncb / 4;                  // >= 4 channel blocks (36 k-steps) per split: 256->1024 @16^2 at 2 per split lost 12 %
-    if (ks < 2 || tiles * ks < 128) return 1;
-    return ks;
-}
-
-// the un-split kernel pays from 128 tiles on: at 128-255 (the 16x16 level of ADM-256 at B = 16) half the CUs idle, and it still
-// beats conv_fast + split-K + reduce (1024->1024: 100 vs 114 us, 512->1024: 55 vs 70, 256->1024: 34 vs 52; 2048->1024 level)
-static bool halo_plain_ok(const KParams& p, int dtype) {
-    bool forced = false;
-    if (!halo_eligible(p, dtype, &forced)) return false;
-    return forced || halo_tiles(p) >= 128;
-}
-
-int nlc_conv_halo_plain_ok(const KParams& p, int dtype) { return halo_plain_ok(p, dtype) ? 1 : 0; }
-
-int nlc_conv_halo_prologue_ok(const KParams& p, int dtype) {
-    return dtype == NLC_BF16 && halo_plain_ok(p, dtype) ? 1 : 0;
-}
-
-// GroupNorm statistics ride along when the halo kernel runs in 16 bits with NHWC output and whole 128-channel N-tiles (split-K
-// launches too: from the epilogue of the workgroup that arrives last at the tile)
-int nlc_conv_halo_stats_partials(const KParams& p, int dtype) {
-    if (!nlc_is16(dtype) || p.out_mode != NLC_OUT_NHWC || (p.Cout % BN) != 0) return 0;
-    if (nlc_conv_halo_ksplit(p, dtype) <= 1 && !halo_plain_ok(p, dtype)) return 0;
-    return 1;
-}
-
-// 3x3 / stride 1 / pad 1 (optionally on the nearest-2x upsampled input), output H and W multiples of 16, enough tiles to fill the chip.
-// nlc_conv_desc.policy: NLC_CONV_NO_HALO disables, NLC_CONV_FORCE_HALO forces (for eligible shapes) regardless of the tile count.
-// p.ksplit > 1 (set by nlc_conv2d when nlc_conv_halo_ksplit asks for it and the caller passed the workspace): split-K + reduce.
-int nlc_conv_halo_dispatch(const KParams& p, int dtype, hipStream_t stream) {
+// p.ksplit > 1 (the planner's HALO_SPLIT, p.partial = the caller's workspace): split-K, reduced by the workgroup that arrives last.
+int nlc_conv_halo_launch(const KParams& p, int dtype, hipStream_t stream) {
     if (p.ksplit > 1) {
-        if (nlc_conv_halo_ksplit(p, dtype) != p.ksplit || !p.partial) return NLC_EUNSUPPORTED;
+        NLC_REQUIRE(nlc_is16(dtype) && p.partial && !p.gn_coef && (p.Cout % BN) == 0, "nlc_conv2d(halo): internal: planner/kernel disagreement (split-K)");
         if (dtype == NLC_F16) return launch_halo<f16_raw, false, true>(p, stream);
         return launch_halo<bf16_raw, false, true>(p, stream);
     }
-    if (!halo_plain_ok(p, dtype)) return NLC_EUNSUPPORTED;
+    NLC_REQUIRE(!p.gn_coef || dtype == NLC_BF16, "nlc_conv2d(halo): internal: planner/kernel disagreement (prologue)");
     // CF instantiation: whole N-tiles, bias (and embedding) readable as aligned float4
     const int kbe = MmaH<bf16_raw>::KBE;
     const bool cf = nlc_is16(dtype) && !p.gn_coef && (p.Cout % BN) == 0 && p.bias && (reinterpret_cast<uintptr_t>(p.bias) & 15) == 0 &&
                     p.out_mode == NLC_OUT_NHWC && p.act == NLC_ACT_NONE && p.Cin_pad / kbe >= 2 && !(p.C1 > 0 && p.C0 / kbe == 1) &&
                     (!p.emb || ((reinterpret_cast<uintptr_t>(p.emb) & 15) == 0 && (p.emb_stride & 3) == 0));
     if (dtype == NLC_BF16) return p.gn_coef ? launch_halo<bf16_raw, true>(p, stream) : cf ? launch_halo<bf16_raw, false, false, false, true>(p, stream) : launch_halo<bf16_raw, false>(p, stream);
-    if (dtype == NLC_F16) return cf ? launch_halo<f16_raw, false, false, false, true>(p, stream) : launch_halo<f16_raw, false>(p, stream);      // (GroupNorm prologue: bf16 instantiation only - it is off by default)
+    if (dtype == NLC_F16) return cf ? launch_halo<f16_raw, false, false, false, true>(p, stream) : launch_halo<f16_raw, false>(p, stream);
     if (p.math == NLC_MATH_F16X3) return launch_halo<float, false, false, true>(p, stream);
     return launch_halo<float, false>(p, stream);
 }

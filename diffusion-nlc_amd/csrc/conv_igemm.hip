@@ -278,19 +278,127 @@ static bool desc_sane(const nlc_conv_desc* d, int dtype) {
     return d && nlc_dtype_ok(dtype) && d->B > 0 && d->Hout > 0 && d->Wout > 0 && d->Cout > 0 && d->policy != NLC_CONV_GENERIC;
 }
 
-// The small-map 3x3 kernel (conv_small.hip) takes a launch when the caller asks for it - a GroupNorm of the input to apply on the way
-// into LDS (nlc_conv_desc.gn_in) or policy NLC_CONV_FORCE_SMALL - and the geometry fits; tuning bit 21 = never (A/B).
-static bool small_wanted(const nlc_conv_desc* d, const KParams& p, int dtype, SmallGeom& g) {
-    if (!(d->gn_in || d->policy == NLC_CONV_FORCE_SMALL) || (d->tuning & (1 << 21))) return false;
-    return nlc_conv_small_geom(p, dtype, g);
+// ---- THE dispatch decision of nlc_conv2d.  The launch runs exactly the kernel planned here and the five host queries return fields of
+//      the same plan, so a query cannot answer for a kernel the launch does not pick.  nlc_conv_desc.policy, the selection bits of
+//      tuning and the tile-count thresholds are read here and nowhere else; the kernel files answer for their own limits (conv_params.h).
+enum ConvKernel { K_SMALL, K_NARROW, K_HALO_SPLIT, K_HALO, K_PW, K_FAST, K_GENERIC };
+struct ConvPlan {
+    ConvKernel kernel;
+    int ksplit;                 // k-slices of that kernel (1 = none)
+    int64_t workspace_bytes;    // workspace those slices need (0 = none)
+    bool stats;                 // the kernel adds the ride-along GroupNorm totals (stats_out)
+    bool prologue, norm_out;    // the kernel honours the descriptor's gn_coef / norm_out
+    bool split_declined;        // the halo kernel would have split K but the workspace at hand is too small, and another kernel runs instead
+    SmallGeom small;            // K_SMALL only
+};
+
+// A split launch's workspace: the arrival counters (4 KiB in front) + ks f32 copies of the output as the kernel tiles it
+static int64_t split_bytes(int ks, int64_t rows, int64_t cols) {
+    return ks > 1 ? ks * rows * cols * (int64_t)sizeof(float) + 4096 : 0;
+}
+
+// p: fill_params of the descriptor; gn_in: it carries (or, for a query, is imagined to carry) nlc_conv_desc.gn_in; ws_bytes: workspace
+// the caller passed (the queries: unlimited - passing the workspace they size is the caller's opt-in to split-K).  In dispatch order:
+static ConvPlan plan_conv(const KParams& p, bool gn_in, int dtype, int64_t ws_bytes) {
+    ConvPlan pl{};
+    pl.kernel = K_GENERIC; pl.ksplit = 1;
+    // Ride-along statistics, for every kernel that has them (small, halo, pointwise, fast): 16-bit NHWC output in whole 128-channel N-tiles
+    const bool stats16 = nlc_is16(dtype) && p.out_mode == NLC_OUT_NHWC && (p.Cout % BN) == 0;
+    const bool no_split = (p.tuning & 2048) != 0;                // tuning bit 11: no split-K in the halo and fast kernels (A/B, stress test)
+
+    // small-map 3x3 (conv_small.hip): when the caller asks for it - a GroupNorm of the input to apply on the way into LDS (gn_in; an
+    // explicit request, honoured under every policy) or policy NLC_CONV_FORCE_SMALL - and the geometry fits; tuning bit 21 = never (A/B).
+    // Its k-slices are part of the geometry: a launch without their workspace is refused, not re-planned.
+    if ((gn_in || p.policy == NLC_CONV_FORCE_SMALL) && !(p.tuning & (1 << 21)) && nlc_conv_small_geom(p, dtype, pl.small)) {
+        pl.kernel = K_SMALL; pl.ksplit = pl.small.ks;
+        pl.workspace_bytes = split_bytes(pl.ksplit, p.M, (int64_t)p.NT * BN);
+        pl.stats = stats16;
+        return pl;
+    }
+    if (p.policy == NLC_CONV_GENERIC) return pl;                 // (A/B runs)
+
+    // <= 16 output channels (conv_narrow.hip): policy AUTO only, from 64 patches on; tuning bit 9 = never (A/B)
+    if (p.policy == NLC_CONV_AUTO && !(p.tuning & 512) && nlc_conv_narrow_tiles(p, dtype) >= 64) { pl.kernel = K_NARROW; return pl; }
+
+    // LDS-halo 3x3 (conv_halo.hip); policy NLC_CONV_NO_HALO disables, NLC_CONV_FORCE_HALO takes every shape it can whatever the tile count
+    HaloShape h;
+    if (p.policy != NLC_CONV_NO_HALO && nlc_conv_halo_shape(p, dtype, h)) {
+        // split-K: fewer tiles than CUs and a long K - the 16x16 level of ADM-256 at B = 16 (1024->1024: 128 tiles x 2, 1024->512: 64
+        // tiles x 4); tuning bit 7 disables it (A/B)
+        int ks = 1;
+        if (!no_split && !(p.tuning & 128) && h.tiles < 256) {
+            ks = 256 / h.tiles < h.max_ksplit ? 256 / h.tiles : h.max_ksplit;
+            if (ks < 2 || h.tiles * ks < 128) ks = 1;
+        }
+        const int64_t need = split_bytes(ks, p.M, p.Cout);
+        if (ks > 1 && ws_bytes >= need) {
+            pl.kernel = K_HALO_SPLIT; pl.ksplit = ks; pl.workspace_bytes = need; pl.stats = stats16;
+            return pl;
+        }
+        // the un-split kernel pays from 128 tiles on: at 128-255 (the 16x16 level of ADM-256 at B = 16) half the CUs idle, and it still
+        // beats conv_fast + split-K + reduce (1024->1024: 100 vs 114 us, 512->1024: 55 vs 70, 256->1024: 34 vs 52; 2048->1024 level)
+        if (p.policy == NLC_CONV_FORCE_HALO || h.tiles >= 128) {
+            pl.kernel = K_HALO; pl.stats = stats16; pl.prologue = h.prologue;
+            return pl;
+        }
+        pl.split_declined = ks > 1;
+    }
+
+    // persistent pointwise (conv_pw.hip): static tile ranges pay from 768 tiles on; below, conv_fast's one-tile workgroups are level or
+    // ahead (32x32, B = 16: 24 us both); tuning bit 15 = never (A/B against conv_fast)
+    if (!(p.tuning & 32768) && nlc_conv_pw_tiles(p, dtype) >= 768) {
+        pl.kernel = K_PW; pl.stats = stats16;
+        pl.norm_out = p.norm_out && nlc_conv_pw_norm_ok(p);
+        return pl;
+    }
+
+    // LDS-DMA implicit GEMM (conv_fast.hip): split-K (the f32 parity path never passes a workspace) for shapes with fewer output tiles
+    // than 2 workgroups per CU and a long K; tuning bit 14 = aim at one per CU (A/B)
+    if (nlc_conv_fast_shape(p)) {
+        pl.kernel = K_FAST; pl.stats = stats16;
+        const int ks = no_split ? 1 : nlc_conv_fast_ksplit(p, dtype, (p.tuning & 16384) ? 256 : 512);
+        const int64_t need = split_bytes(ks, (int64_t)p.MT * BM, (int64_t)p.NT * BN);
+        if (ks > 1 && ws_bytes >= need) { pl.ksplit = ks; pl.workspace_bytes = need; }
+        return pl;
+    }
+    return pl;                                                   // generic register-staged kernel (this file): everything else
+}
+
+// A host query = the plan of the descriptor as the caller WOULD launch it: h = *d with the attachment asked about filled in
+static ConvPlan plan_query(const nlc_conv_desc* d, int dtype, bool gn_in) {
+    KParams p{};
+    fill_params(d, p);
+    return plan_conv(p, gn_in, dtype, INT64_MAX);
+}
+static void* const kImagined = reinterpret_cast<void*>(16);      // an attachment that does not exist yet: only its presence is planned with
+
+extern "C" int64_t nlc_conv2d_workspace_bytes(const nlc_conv_desc* d, int dtype) {
+    return desc_sane(d, dtype) ? plan_query(d, dtype, d->gn_in != nullptr).workspace_bytes : 0;
+}
+
+extern "C" int nlc_conv2d_stats_partials(const nlc_conv_desc* d, int dtype) {
+    return desc_sane(d, dtype) && plan_query(d, dtype, d->gn_in != nullptr).stats ? 1 : 0;
 }
 
 extern "C" int nlc_conv2d_gn_in_supported(const nlc_conv_desc* d, int dtype) {
-    if (!desc_sane(d, dtype) || (d->tuning & (1 << 21))) return 0;
-    KParams p{};
-    fill_params(d, p);
-    SmallGeom g;
-    return nlc_conv_small_geom(p, dtype, g) ? 1 : 0;
+    return desc_sane(d, dtype) && plan_query(d, dtype, true).kernel == K_SMALL ? 1 : 0;
+}
+
+extern "C" int nlc_conv2d_norm_out_supported(const nlc_conv_desc* d, int dtype) {
+    if (!desc_sane(d, dtype)) return 0;
+    nlc_conv_desc h = *d;
+    h.norm_out = kImagined; h.gn_coef = (const float*)kImagined;
+    return plan_query(&h, dtype, false).norm_out ? 1 : 0;
+}
+
+extern "C" int nlc_conv2d_prologue_supported(const nlc_conv_desc* d, int dtype) {
+    if (!desc_sane(d, dtype)) return 0;
+    nlc_conv_desc h = *d;
+    h.norm_out = nullptr; h.gn_coef = nullptr;
+    // a launch the narrow kernel takes is left to it (with the separate normalisation pass): bringing gn_coef would move it to the halo kernel
+    if (plan_query(&h, dtype, false).kernel == K_NARROW) return 0;
+    h.gn_coef = (const float*)kImagined;
+    return plan_query(&h, dtype, false).prologue ? 1 : 0;
 }
 
 // nlc_gn_in -> the kernel's view (validated)
@@ -313,48 +421,6 @@ static int fill_gn_in(const nlc_gn_in* q, const KParams& p, GnIn& g) {
     g.eps = q->eps; g.gamma = q->gamma; g.beta = q->beta; g.scale = q->scale; g.shift = q->shift; g.ss_stride = q->ss_stride;
     g.act = q->act; g.div_gs = FastDiv::make(gs);
     return NLC_OK;
-}
-
-extern "C" int64_t nlc_conv2d_workspace_bytes(const nlc_conv_desc* d, int dtype) {
-    if (!desc_sane(d, dtype)) return 0;
-    KParams p{};
-    fill_params(d, p);
-    { SmallGeom sg; if (small_wanted(d, p, dtype, sg)) return nlc_conv_small_split_bytes(p, sg); }
-    if (nlc_conv_narrow_ok(p, dtype)) return 0;
-    const int64_t M64 = (int64_t)d->B * d->Hout * d->Wout;
-    const int ks = nlc_conv_halo_ksplit(p, dtype);
-    if (ks > 1) return (int64_t)ks * M64 * d->Cout * (int64_t)sizeof(float) + 4096;      // arrival counters in front of the halo kernel's partial sums
-    if (nlc_conv_halo_plain_ok(p, dtype)) return 0;
-    return nlc_conv_fast_split_bytes(p, nlc_conv_fast_ksplit(p, dtype));
-}
-
-extern "C" int nlc_conv2d_stats_partials(const nlc_conv_desc* d, int dtype) {
-    if (!desc_sane(d, dtype)) return 0;
-    KParams p{};
-    fill_params(d, p);
-    // (the small-map kernel is asked first, as in nlc_conv2d and nlc_conv2d_workspace_bytes: it adds totals to whole 128-channel tiles)
-    { SmallGeom sg; if (small_wanted(d, p, dtype, sg)) return p.Cout % BN == 0 ? 1 : 0; }
-    if (nlc_conv_narrow_ok(p, dtype)) return 0;          // the <= 16-channel kernel emits none
-    const int P = nlc_conv_halo_stats_partials(p, dtype);
-    if (P > 0) return P;
-    return nlc_conv_fast_stats_partials(p, dtype);
-}
-
-extern "C" int nlc_conv2d_norm_out_supported(const nlc_conv_desc* d, int dtype) {
-    if (!desc_sane(d, dtype)) return 0;
-    KParams p{};
-    fill_params(d, p);
-    if (nlc_conv_narrow_ok(p, dtype)) return 0;
-    return nlc_conv_pw_norm_ok(p, dtype);
-}
-
-extern "C" int nlc_conv2d_prologue_supported(const nlc_conv_desc* d, int dtype) {
-    if (!desc_sane(d, dtype)) return 0;
-    KParams p{};
-    fill_params(d, p);
-    p.gn_coef = nullptr; p.norm_out = nullptr;           // "the gn_* fields themselves are not looked at"
-    if (nlc_conv_narrow_ok(p, dtype)) return 0;
-    return nlc_conv_halo_prologue_ok(p, dtype);
 }
 
 // nlc_conv_desc.debug bit 1 (NLC_MATH_F16X3): the operand split needs |x| < 65504 (include/nlc_hip.h).  max |x| over the input
@@ -443,23 +509,43 @@ static int validate_conv_desc(const nlc_conv_desc* d, int dtype) {
     return NLC_OK;
 }
 
-// The small-map kernel's parameter block for this descriptor: NLC_OK (sp filled), NLC_EUNSUPPORTED (not a small-map launch), or an error
-static int prepare_small(const nlc_conv_desc* d, const KParams& p, int dtype, hipStream_t stream, SmallParams& sp) {
-    if (!small_wanted(d, p, dtype, sp.geo)) return NLC_EUNSUPPORTED;
-    sp.k = p;
-    if (d->gn_in) { const int gr = fill_gn_in(d->gn_in, p, sp.gn); if (gr != NLC_OK) return gr; }
+// Steps 3 and 4 of nlc_conv2d (shared with nlc_resblock_small): the plan of the launch as the descriptor stands ...
+static ConvPlan plan_launch(const nlc_conv_desc* d, const KParams& p, int dtype) {
+    return plan_conv(p, d->gn_in != nullptr, dtype, d->workspace ? d->workspace_bytes : 0);
+}
+// ... and every optional attachment of the descriptor checked against it and hooked into the parameter block.  NLC_OK: p is what the
+// planned kernel gets.
+static int attach(const nlc_conv_desc* d, KParams& p, const ConvPlan& pl, hipStream_t stream) {
+    NLC_REQUIRE(!d->gn_in || pl.kernel == K_SMALL, "nlc_conv2d: gn_in given but this launch cannot apply it (ask nlc_conv2d_gn_in_supported first)");
     if (d->stats_out) {
+        NLC_REQUIRE(pl.stats, "nlc_conv2d: stats_out given but this launch does not emit statistics (ask nlc_conv2d_stats_partials first)");
+        NLC_REQUIRE(!pl.split_declined, "nlc_conv2d: stats_out on a split-K shape needs the workspace of nlc_conv2d_workspace_bytes");
         NLC_REQUIRE(d->stats_bytes >= (int64_t)p.B * (p.Cout / p.stats_gran) * 4 * (int64_t)sizeof(long long), "nlc_conv2d: stats_out too small");
         NLC_REQUIRE((reinterpret_cast<uintptr_t>(d->stats_out) & 15) == 0, "nlc_conv2d: stats_out must be 16-byte aligned (its consumers read 16-byte pairs)");
-        sp.k.stats = (long long*)d->stats_out;
+        p.stats = (long long*)d->stats_out;
     }
-    if (sp.geo.ks > 1) {
-        NLC_REQUIRE(d->workspace && d->workspace_bytes >= nlc_conv_small_split_bytes(p, sp.geo),
-                    "nlc_conv2d: this small-map launch splits K %d ways: it needs the workspace of nlc_conv2d_workspace_bytes", sp.geo.ks);
-        sp.k.partial = (float*)d->workspace;
-        if (d->debug & 1) { const int cr = check_counters(sp.k, stream); if (cr != NLC_OK) return cr; }
+    if (p.norm_out) {                                // pointwise launch that also writes act(GroupNorm(x)) of its input
+        NLC_REQUIRE(p.gn_coef, "nlc_conv2d: norm_out needs gn_coef (nlc_groupnorm_coef)");
+        NLC_REQUIRE((reinterpret_cast<uintptr_t>(p.norm_out) & 15) == 0, "nlc_conv2d: norm_out must be 16-byte aligned");
+        NLC_REQUIRE(pl.norm_out, "nlc_conv2d: norm_out given but this launch cannot write it (ask nlc_conv2d_norm_out_supported first)");
+    } else {
+        NLC_REQUIRE(!p.gn_coef || pl.prologue, "nlc_conv2d: gn_coef given but this launch has no GroupNorm prologue (ask nlc_conv2d_prologue_supported first)");
+    }
+    if (pl.ksplit > 1) {
+        // (only the small-map kernel can miss its workspace: the halo and fast kernels' splits are planned from the workspace at hand)
+        NLC_REQUIRE(d->workspace && d->workspace_bytes >= pl.workspace_bytes,
+                    "nlc_conv2d: this small-map launch splits K %d ways: it needs the workspace of nlc_conv2d_workspace_bytes", pl.ksplit);
+        p.partial = (float*)d->workspace;
+        if (pl.kernel != K_SMALL) p.ksplit = pl.ksplit;          // (the small-map kernel reads its k-slices from the geometry)
+        if (d->debug & 1) { const int cr = check_counters(p, stream); if (cr != NLC_OK) return cr; }
     }
     return NLC_OK;
+}
+
+// The small-map kernel's parameter block from an attached K_SMALL plan
+static int small_params(const nlc_conv_desc* d, const KParams& p, const ConvPlan& pl, SmallParams& sp) {
+    sp.k = p; sp.geo = pl.small;
+    return d->gn_in ? fill_gn_in(d->gn_in, p, sp.gn) : NLC_OK;
 }
 
 extern "C" int nlc_resblock_small(const nlc_conv_desc* d1, const nlc_conv_desc* d2, void* barrier, int dtype, void* stream) {
@@ -470,91 +556,50 @@ extern "C" int nlc_resblock_small(const nlc_conv_desc* d1, const nlc_conv_desc* 
     NLC_REQUIRE(barrier && (reinterpret_cast<uintptr_t>(barrier) & 7) == 0, "nlc_resblock_small: barrier must be two zeroed, 8-byte aligned ints");
     NLC_REQUIRE(d2->x0 == d1->out && !d2->x1, "nlc_resblock_small: the second convolution's input must be the first one's output");
     NLC_REQUIRE(d1->workspace == d2->workspace, "nlc_resblock_small: both convolutions use ONE split-K workspace (the phases do not overlap)");
-    KParams p1, p2;
-    fill_params(d1, p1);
-    fill_params(d2, p2);
-    SmallParams s1{}, s2{};
-    rc = prepare_small(d1, p1, dtype, (hipStream_t)stream, s1);
-    if (rc != NLC_OK) { if (rc == NLC_EUNSUPPORTED) nlc_set_error("nlc_resblock_small: the first convolution is not a small-map launch"); return rc; }
-    rc = prepare_small(d2, p2, dtype, (hipStream_t)stream, s2);
-    if (rc != NLC_OK) { if (rc == NLC_EUNSUPPORTED) nlc_set_error("nlc_resblock_small: the second convolution is not a small-map launch"); return rc; }
-    s1.out_sc1 = 1;                                  // h crosses the grid barrier to other CUs: write-through
-    rc = nlc_resblock_small_dispatch(s1, s2, (int*)barrier, dtype, (hipStream_t)stream);
+    const nlc_conv_desc* ds[2] = {d1, d2};
+    SmallParams sp[2] = {};
+    for (int i = 0; i < 2; ++i) {
+        KParams p;
+        fill_params(ds[i], p);
+        const ConvPlan pl = plan_launch(ds[i], p, dtype);
+        if (pl.kernel != K_SMALL) {
+            nlc_set_error("nlc_resblock_small: the %s convolution is not a small-map launch", i ? "second" : "first");
+            return NLC_EUNSUPPORTED;
+        }
+        rc = attach(ds[i], p, pl, (hipStream_t)stream);
+        if (rc == NLC_OK) rc = small_params(ds[i], p, pl, sp[i]);
+        if (rc != NLC_OK) return rc;
+    }
+    sp[0].out_sc1 = 1;                               // h crosses the grid barrier to other CUs: write-through
+    rc = nlc_resblock_small_dispatch(sp[0], sp[1], (int*)barrier, dtype, (hipStream_t)stream);
     if (rc == NLC_EUNSUPPORTED) nlc_set_error("nlc_resblock_small: no one-launch form for this geometry (the two convolutions must tile alike and the grid must be resident at once)");
     return rc;
 }
 
-extern "C" int nlc_conv2d(const nlc_conv_desc* d, int dtype, void* stream) {
+// Validate the descriptor, fill the parameter block, plan once, check the attachments against the plan, launch the planned kernel.
+extern "C" int nlc_conv2d(const nlc_conv_desc* d, int dtype, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
     { const int vr = validate_conv_desc(d, dtype); if (vr != NLC_OK) return vr; }
-    const int per = nlc_is16(dtype) ? 8 : 4;
-    const int kbe = nlc_is16(dtype) ? Mma<bf16_raw>::KBE : Mma<float>::KBE;
-    (void)per; (void)kbe;
-
-    if ((d->debug & 2) && d->math == NLC_MATH_F16X3) { const int cr = check_x3_domain(d, (hipStream_t)stream); if (cr != NLC_OK) return cr; }
+    if ((d->debug & 2) && d->math == NLC_MATH_F16X3) { const int cr = check_x3_domain(d, stream); if (cr != NLC_OK) return cr; }
     KParams p;
     fill_params(d, p);
-    // stride-1 3x3 / 1x1 "same" convolutions take the LDS-DMA fast path; everything else (strided,
-    // odd kernels, cropped outputs) the generic gather kernel.  policy NLC_CONV_GENERIC forces the latter (A/B runs).
-    const bool force_generic = d->policy == NLC_CONV_GENERIC;
-    {
-        SmallParams sp{};
-        const int pr = prepare_small(d, p, dtype, (hipStream_t)stream, sp);
-        if (pr == NLC_OK) return nlc_conv_small_dispatch(sp, dtype, (hipStream_t)stream);
-        if (pr != NLC_EUNSUPPORTED) return pr;
-        NLC_REQUIRE(!d->gn_in, "nlc_conv2d: gn_in given but this launch cannot apply it (ask nlc_conv2d_gn_in_supported first)");
+    const ConvPlan pl = plan_launch(d, p, dtype);
+    { const int ar = attach(d, p, pl, stream); if (ar != NLC_OK) return ar; }
+    switch (pl.kernel) {
+        case K_SMALL: {
+            SmallParams sp{};
+            const int sr = small_params(d, p, pl, sp);
+            return sr != NLC_OK ? sr : nlc_conv_small_launch(sp, dtype, stream);
+        }
+        case K_NARROW: return nlc_conv_narrow_launch(p, dtype, stream);
+        case K_HALO_SPLIT:
+        case K_HALO: return nlc_conv_halo_launch(p, dtype, stream);
+        case K_PW: return nlc_conv_pw_launch(p, dtype, stream);
+        case K_FAST: return nlc_conv_fast_launch(p, dtype, stream);
+        case K_GENERIC: break;
     }
-    if (!force_generic) {
-        int Pfast = 0;
-        if (d->stats_out) {
-            const int Phalo = nlc_conv_halo_stats_partials(p, dtype);
-            Pfast = Phalo > 0 ? 0 : nlc_conv_fast_stats_partials(p, dtype);
-            const int P = nlc_conv_narrow_ok(p, dtype) ? 0 : (Phalo > 0 ? Phalo : Pfast);
-            NLC_REQUIRE(P > 0, "nlc_conv2d: stats_out given but this launch does not emit statistics (ask nlc_conv2d_stats_partials first)");
-            NLC_REQUIRE(d->stats_bytes >= (int64_t)p.B * (p.Cout / p.stats_gran) * 4 * (int64_t)sizeof(long long), "nlc_conv2d: stats_out too small");
-            NLC_REQUIRE((reinterpret_cast<uintptr_t>(d->stats_out) & 15) == 0, "nlc_conv2d: stats_out must be 16-byte aligned (its consumers read 16-byte pairs)");
-            p.stats = (long long*)d->stats_out;
-        }
-        if (p.norm_out) {                            // pointwise launch that also writes act(GroupNorm(x)) of its input
-            NLC_REQUIRE(p.gn_coef, "nlc_conv2d: norm_out needs gn_coef (nlc_groupnorm_coef)");
-            NLC_REQUIRE((reinterpret_cast<uintptr_t>(p.norm_out) & 15) == 0, "nlc_conv2d: norm_out must be 16-byte aligned");
-            NLC_REQUIRE(nlc_conv_pw_norm_ok(p, dtype),
-                        "nlc_conv2d: norm_out given but this launch cannot write it (ask nlc_conv2d_norm_out_supported first)");
-            if (!Pfast) p.stats = nullptr;
-            return nlc_conv_pw_dispatch(p, dtype, (hipStream_t)stream);
-        }
-        NLC_REQUIRE(!p.gn_coef || nlc_conv_halo_prologue_ok(p, dtype),
-                    "nlc_conv2d: gn_coef given but this launch has no GroupNorm prologue (ask nlc_conv2d_prologue_supported first)");
-        int rc = nlc_conv_narrow_dispatch(p, dtype, (hipStream_t)stream);
-        if (rc != NLC_EUNSUPPORTED) return rc;
-        const int hks = nlc_conv_halo_ksplit(p, dtype);
-        if (hks > 1 && d->workspace && d->workspace_bytes >= (int64_t)hks * p.M * p.Cout * (int64_t)sizeof(float) + 4096) {
-            p.ksplit = hks; p.partial = (float*)d->workspace;
-            if (d->debug & 1) { const int cr = check_counters(p, (hipStream_t)stream); if (cr != NLC_OK) return cr; }
-        } else {
-            NLC_REQUIRE(hks <= 1 || !d->stats_out || nlc_conv_halo_plain_ok(p, dtype), "nlc_conv2d: stats_out on a split-K shape needs the workspace of nlc_conv2d_workspace_bytes");
-        }
-        rc = nlc_conv_halo_dispatch(p, dtype, (hipStream_t)stream);
-        if (rc != NLC_EUNSUPPORTED) return rc;
-        p.ksplit = 1; p.partial = nullptr;
-        if (!Pfast) p.stats = nullptr;
-        rc = nlc_conv_pw_dispatch(p, dtype, (hipStream_t)stream);         // 1x1 with >= 1024 tiles: the persistent pointwise kernel
-        if (rc != NLC_EUNSUPPORTED) return rc;
-        if (d->workspace) {                          // split-K needs [ksplit][M][Cout] f32 of caller workspace
-            const int ks = nlc_conv_fast_ksplit(p, dtype);
-            if (ks > 1 && d->workspace_bytes >= nlc_conv_fast_split_bytes(p, ks)) {
-                p.ksplit = ks; p.partial = (float*)d->workspace;
-                if (d->debug & 1) { const int cr = check_counters(p, (hipStream_t)stream); if (cr != NLC_OK) return cr; }
-            }
-        }
-        rc = nlc_conv_fast_dispatch(p, dtype, (hipStream_t)stream);
-        if (rc != NLC_EUNSUPPORTED) return rc;
-        p.ksplit = 1; p.partial = nullptr;
-    }
-    NLC_REQUIRE(!p.norm_out, "nlc_conv2d: norm_out given but this launch cannot write it");
-    NLC_REQUIRE(!p.gn_coef, "nlc_conv2d: gn_coef given but this launch has no GroupNorm prologue");
-    NLC_REQUIRE(!p.stats, "nlc_conv2d: stats_out given but the generic kernel emits no statistics");
-    if (dtype == NLC_BF16) return launch<bf16_raw>(p, (hipStream_t)stream);
-    if (dtype == NLC_F16) return launch<f16_raw>(p, (hipStream_t)stream);
-    if (p.math == NLC_MATH_F16X3) return launch<float, true>(p, (hipStream_t)stream);
-    return launch<float>(p, (hipStream_t)stream);
+    if (dtype == NLC_BF16) return launch<bf16_raw>(p, stream);
+    if (dtype == NLC_F16) return launch<f16_raw>(p, stream);
+    if (p.math == NLC_MATH_F16X3) return launch<float, true>(p, stream);
+    return launch<float>(p, stream);
 }

@@ -175,22 +175,21 @@ __global__ __launch_bounds__(NTH, 1) void conv_narrow_kernel(const KParams p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-bool narrow_eligible(const KParams& p, int dtype) {
-    if (!nlc_is16(dtype) || p.policy != NLC_CONV_AUTO || (p.tuning & 512)) return false;       // tuning bit 9: A/B switch
-    if (!(p.KH == 3 && p.KW == 3 && p.pad_t == 1 && p.pad_l == 1 && p.stride == 1) || p.ups) return false;
-    if (p.Cout > 16 || p.Cout_pad < 16 || p.C1 != 0 || p.C0 % 64 || p.C0 / 64 > 128) return false;
-    if (p.Hout % PATCH || p.Wout % PATCH || p.Hout != p.Hin || p.Wout != p.Win) return false;
-    if (p.emb || p.res || p.act != NLC_ACT_NONE || p.gn_coef) return false;
-    if ((int64_t)p.B * p.Hout * p.Wout >= (1ll << 31)) return false;
-    return p.B * (p.Hout / PATCH) * (p.Wout / PATCH) >= 64;
-}
-
 }  // namespace
 
-int nlc_conv_narrow_ok(const KParams& p, int dtype) { return narrow_eligible(p, dtype) ? 1 : 0; }
+// 16x16 patches of this launch, 0: the kernel does not take it (conv_params.h; from how many patches on it pays is the planner's business)
+int nlc_conv_narrow_tiles(const KParams& p, int dtype) {
+    if (!nlc_is16(dtype)) return 0;
+    if (!(p.KH == 3 && p.KW == 3 && p.pad_t == 1 && p.pad_l == 1 && p.stride == 1) || p.ups) return 0;
+    if (p.Cout > 16 || p.Cout_pad < 16 || p.C1 != 0 || p.C0 % 64 || p.C0 / 64 > 128) return 0;
+    if (p.Hout % PATCH || p.Wout % PATCH || p.Hout != p.Hin || p.Wout != p.Win) return 0;
+    if (p.emb || p.res || p.act != NLC_ACT_NONE || p.gn_coef) return 0;
+    if ((int64_t)p.B * p.Hout * p.Wout >= (1ll << 31)) return 0;
+    return p.B * (p.Hout / PATCH) * (p.Wout / PATCH);
+}
 
-int nlc_conv_narrow_dispatch(const KParams& p, int dtype, hipStream_t stream) {
-    if (!narrow_eligible(p, dtype) || p.stats) return NLC_EUNSUPPORTED;
+int nlc_conv_narrow_launch(const KParams& p, int dtype, hipStream_t stream) {
+    NLC_REQUIRE(nlc_is16(dtype) && p.Cout <= 16 && !p.stats && !p.gn_coef, "nlc_conv2d(narrow): internal: planner/kernel disagreement");
     static DeviceOnce once;
     const int slot = nlc_device_once(once, [] {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_narrow_kernel<bf16_raw>), hipFuncAttributeMaxDynamicSharedMemorySize, NARROW_LDS);

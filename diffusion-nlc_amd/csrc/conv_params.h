@@ -226,26 +226,28 @@ __device__ __forceinline__ int64_t res_row_m(const KParams& p, int64_t m) {
     return ((int64_t)b * (p.Hout >> 1) + (y >> 1)) * (p.Wout >> 1) + (x >> 1);
 }
 
-// conv_fast.hip: NLC_OK, NLC_ELAUNCH, or NLC_EUNSUPPORTED (shape not handled -> use the generic kernel)
-int nlc_conv_fast_dispatch(const KParams& p, int dtype, hipStream_t stream);
-// split-K policy for the shapes conv_fast takes (few output tiles, long K): number of splits, 1 = none
-int nlc_conv_fast_ksplit(const KParams& p, int dtype);
-int64_t nlc_conv_fast_split_bytes(const KParams& p, int ks);     // workspace bytes of a conv_fast launch split ks ways
-// conv_halo.hip: split-K factor of the halo kernel for this launch (1 = none): fewer tiles than CUs, long K, bf16, Cout % 128 == 0
-int nlc_conv_halo_ksplit(const KParams& p, int dtype);
-int nlc_conv_halo_plain_ok(const KParams& p, int dtype);          // the un-split halo kernel would take this launch
-// conv_fast.hip: same for the fast path (0 when K would be split or a tile could straddle two images)
-int nlc_conv_fast_stats_partials(const KParams& p, int dtype);
-// conv_halo.hip: partials per image the halo kernel would emit GroupNorm statistics with for this launch (0: it would not)
-int nlc_conv_halo_stats_partials(const KParams& p, int dtype);
-// conv_pw.hip: persistent pointwise (1x1) kernel for launches with many tiles; same return convention as the dispatchers below
-int nlc_conv_pw_ok(const KParams& p, int dtype);
-int nlc_conv_pw_dispatch(const KParams& p, int dtype, hipStream_t stream);
-int nlc_conv_pw_norm_ok(const KParams& p, int dtype);    // 1 if the launch can write nlc_conv_desc.norm_out
-// conv_narrow.hip: 3x3 with at most 16 output channels (the networks' last layer)
-int nlc_conv_narrow_ok(const KParams& p, int dtype);
-int nlc_conv_narrow_dispatch(const KParams& p, int dtype, hipStream_t stream);
-// conv_halo.hip: 1 if the halo kernel would take this launch AND can apply a GroupNorm prologue (bf16)
-int nlc_conv_halo_prologue_ok(const KParams& p, int dtype);
-// conv_halo.hip: 3x3 with the input halo resident in LDS; same return convention
-int nlc_conv_halo_dispatch(const KParams& p, int dtype, hipStream_t stream);
+// ---- What nlc_conv2d's planner (conv_igemm.hip: plan_conv) asks of each kernel file, and each file's one launch function.  A question is
+//      about the kernel's own limits only - shapes, alignment, instantiations; whether the kernel is the one to run (nlc_conv_desc.policy,
+//      the selection bits of tuning, tile-count thresholds, the statistics rule) is decided in the planner and nowhere else.  A launch
+//      function launches what the plan names: NLC_OK or NLC_ELAUNCH; handed something its own question rejects it returns NLC_EINVAL
+//      ("internal: planner/kernel disagreement"), which no plan can reach.  (conv_small.hip: conv_small.h.)
+// conv_halo.hip: 3x3 with the input halo resident in LDS
+struct HaloShape {
+    int tiles;          // (16x16 patch x 128 cout) tiles
+    int max_ksplit;     // most k-slices its split-K instantiation runs this launch in (<= 1: none)
+    bool prologue;      // it can apply nlc_conv_desc.gn_coef (un-split form)
+};
+bool nlc_conv_halo_shape(const KParams& p, int dtype, HaloShape& h);
+int nlc_conv_halo_launch(const KParams& p, int dtype, hipStream_t stream);
+// conv_fast.hip: 3x3 / 1x1 implicit GEMM; ksplit: k-slices that bring the launch to `target` workgroups (1 = none)
+bool nlc_conv_fast_shape(const KParams& p);
+int nlc_conv_fast_ksplit(const KParams& p, int dtype, int target);
+int nlc_conv_fast_launch(const KParams& p, int dtype, hipStream_t stream);
+// conv_pw.hip: persistent pointwise (1x1) kernel: its tiles for this launch (0: not taken); whether such a launch can also write norm_out
+int64_t nlc_conv_pw_tiles(const KParams& p, int dtype);
+bool nlc_conv_pw_norm_ok(const KParams& p);
+int nlc_conv_pw_launch(const KParams& p, int dtype, hipStream_t stream);
+// conv_narrow.hip: 3x3 with at most 16 output channels (the networks' last layer): its 16x16 patches for this launch (0: not taken)
+int nlc_conv_narrow_tiles(const KParams& p, int dtype);
+int nlc_conv_narrow_launch(const KParams& p, int dtype, hipStream_t stream);
+

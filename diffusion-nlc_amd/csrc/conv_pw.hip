@@ -651,21 +651,20 @@ bool pwr_ok(const KParams& p, int grid) {
 
 }  // namespace
 
-// 1 if the persistent pointwise kernel takes this launch (conv_params.h)
-int nlc_conv_pw_ok(const KParams& p, int dtype) {
-    if (!nlc_is16(dtype) || (p.tuning & 32768)) return 0;                       // tuning bit 15: never (A/B against conv_fast)
-    if (p.policy == NLC_CONV_GENERIC) return 0;
+// Tiles of the persistent pointwise kernel for this launch, 0: it does not take it (conv_params.h; from how many tiles on it pays is the
+// planner's business).  A gn_coef is only taken together with norm_out.
+int64_t nlc_conv_pw_tiles(const KParams& p, int dtype) {
+    if (!nlc_is16(dtype)) return 0;
     if (!(p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad_t == 0 && p.pad_l == 0 && !p.ups)) return 0;
     if (p.Hout != p.Hin || p.Wout != p.Win) return 0;
-    if (p.out_mode != NLC_OUT_NHWC || p.act != NLC_ACT_NONE || p.emb || p.res_ups || (p.gn_coef && !p.norm_out) || p.ksplit > 1) return 0;
+    if (p.out_mode != NLC_OUT_NHWC || p.act != NLC_ACT_NONE || p.emb || p.res_ups || (p.gn_coef && !p.norm_out)) return 0;
     if ((p.Cout % PW_BN) != 0 || (p.C0 % 64) != 0 || (p.C1 % 64) != 0 || p.Cin_pad != p.C0 + p.C1) return 0;
     if (p.bias && (reinterpret_cast<uintptr_t>(p.bias) & 15) != 0) return 0;
     const int HWo = p.Hout * p.Wout;
     if ((p.M & 15) != 0 || (HWo & 15) != 0) return 0;                           // 16-pixel rows never straddle images (statistics)
     if (p.Cin_pad > 768) return 0;        // longer K: the launch is matrix-bound, not latency-bound, and conv_fast's leaner k-loop wins
                                           // (1024 -> 512 @64x64, B = 16: 99 vs 92 us)
-    const int64_t tiles = (int64_t)cdiv(p.M, PW_BM) * (p.Cout / PW_BN);
-    return tiles >= 768 ? 1 : 0;          // static tile ranges; below, conv_fast's one-tile workgroups are level or ahead (32x32, B = 16: 24 us both)
+    return (int64_t)cdiv(p.M, PW_BM) * (p.Cout / PW_BN);
 }
 
 static int pw_grid(const KParams& p) {
@@ -675,28 +674,22 @@ static int pw_grid(const KParams& p) {
     return tiles < 2 * ncu ? tiles : 2 * ncu;                                   // two persistent workgroups per CU
 }
 
-// nlc_conv_desc.norm_out: the resident-weights form, tiles inside one image, the coefficient table of one image in 4 KiB of LDS
-int nlc_conv_pw_norm_ok(const KParams& pin, int dtype) {
-    KParams p = pin;
-    if (!p.norm_out) p.norm_out = reinterpret_cast<char*>(16);                  // (query before the buffer exists)
-    if (!p.gn_coef) p.gn_coef = reinterpret_cast<const float*>(16);
-    if (!nlc_conv_pw_ok(p, dtype) || !pwr_ok(p, pw_grid(p))) return 0;
-    if (((p.Hout * p.Wout) % PR_BM) != 0 || (p.C0 + p.C1) * 8 > PR_COEF_BYTES) return 0;
-    return 1;
+// nlc_conv_desc.norm_out on a launch that nlc_conv_pw_tiles takes: the resident-weights form, tiles inside one image, the coefficient
+// table of one image in 4 KiB of LDS
+bool nlc_conv_pw_norm_ok(const KParams& p) {
+    return pwr_ok(p, pw_grid(p)) && ((p.Hout * p.Wout) % PR_BM) == 0 && (p.C0 + p.C1) * 8 <= PR_COEF_BYTES;
 }
 
-int nlc_conv_pw_dispatch(const KParams& p, int dtype, hipStream_t stream) {
-    if (!nlc_conv_pw_ok(p, dtype)) return NLC_EUNSUPPORTED;
-    if (p.norm_out && !nlc_conv_pw_norm_ok(p, dtype)) return NLC_EUNSUPPORTED;
-    static DeviceOnce once;
-    const int ncu = once.ncu[nlc_device_once(once, [] {})];
+int nlc_conv_pw_launch(const KParams& p, int dtype, hipStream_t stream) {
+    NLC_REQUIRE(nlc_is16(dtype) && p.ksplit == 1 && (!p.gn_coef || p.norm_out), "nlc_conv2d(pointwise): internal: planner/kernel disagreement");
     const int NTn = p.Cout / PW_BN;
     const int tiles = cdiv(p.M, PW_BM) * NTn;
-    const int grid = tiles < 2 * ncu ? tiles : 2 * ncu;                         // two persistent workgroups per CU
+    const int grid = pw_grid(p);
     if (pwr_ok(p, grid)) {
         const int MT = cdiv(p.M, PR_BM);
         return dtype == NLC_BF16 ? launch_pwr_k<bf16_raw>(p, MT, NTn, grid, stream) : launch_pwr_k<f16_raw>(p, MT, NTn, grid, stream);
     }
+    NLC_REQUIRE(!p.norm_out, "nlc_conv2d(pointwise): internal: planner/kernel disagreement (norm_out)");
     // side-by-side walk of the channel tiles (kernel comment): whole groups of NTn workgroups per XCD; tuning bit 17 = never (A/B)
     const int S = grid >> 3;
     const int cowalk = (NTn > 1 && (grid & 7) == 0 && S >= NTn && (S % NTn) == 0 && !(p.tuning & 131072)) ? 1 : 0;

@@ -34,8 +34,10 @@ struct SmallParams {
     int out_sc1;                // stores of the output are write-through (the two-convolution launch hands h to other CUs)
 };
 
+// conv_small.hip, same convention as conv_params.h: the geometry with which the small-map kernel takes this launch (false: it does
+// not), and the launch of a geometry it gave
 bool nlc_conv_small_geom(const KParams& p, int dtype, SmallGeom& g);
-int64_t nlc_conv_small_split_bytes(const KParams& p, const SmallGeom& g);
-int nlc_conv_small_dispatch(const SmallParams& sp, int dtype, hipStream_t stream);
-// one launch for a ResBlock's two convolutions (sp1's output is sp2's input); bar: two zeroed ints
+int nlc_conv_small_launch(const SmallParams& sp, int dtype, hipStream_t stream);
+// one launch for a ResBlock's two convolutions (sp1's output is sp2's input); bar: two zeroed ints.  NLC_EUNSUPPORTED: the two do not
+// tile alike or their grid is not resident at once (nlc_resblock_small's documented answer)
 int nlc_resblock_small_dispatch(const SmallParams& sp1, const SmallParams& sp2, int* bar, int dtype, hipStream_t stream);

@@ -692,17 +692,15 @@ bool nlc_conv_small_geom(const KParams& p, int dtype, SmallGeom& g) {
     return true;
 }
 
-int64_t nlc_conv_small_split_bytes(const KParams& p, const SmallGeom& g) {
-    return g.ks > 1 ? (int64_t)g.ks * p.M * p.NT * BN * (int64_t)sizeof(float) + 4096 : 0;
-}
-
-int nlc_conv_small_dispatch(const SmallParams& sp, int dtype, hipStream_t stream) {
+int nlc_conv_small_launch(const SmallParams& sp, int dtype, hipStream_t stream) {
     const int wm = sp.geo.wm, st = sp.geo.nwst;
+    NLC_REQUIRE(nlc_is16(dtype) && (sp.geo.ks == 1 || sp.k.partial), "nlc_conv2d(small): internal: planner/kernel disagreement");
 #define NLC_SMALL_CASE(WMV, STV) if (wm == WMV && st == STV) { NLC_SWITCH_16(dtype, return (launch_small<T16, WMV, STV>(sp, stream))); }
     NLC_SMALL_CASE(2, 3) NLC_SMALL_CASE(2, 4) NLC_SMALL_CASE(2, 6) NLC_SMALL_CASE(2, 8)
     NLC_SMALL_CASE(4, 3) NLC_SMALL_CASE(4, 4) NLC_SMALL_CASE(4, 6) NLC_SMALL_CASE(4, 8)
 #undef NLC_SMALL_CASE
-    return NLC_EUNSUPPORTED;
+    nlc_set_error("nlc_conv2d(small): internal: planner/kernel disagreement (no instantiation for wm=%d, %d weight stages)", wm, st);
+    return NLC_EINVAL;
 }
 
 // Both convolutions of a ResBlock in one launch: same geometry for both (Cin == Cout, no projection), a grid that is resident at once.

@@ -177,7 +177,7 @@ typedef struct nlc_conv_desc {
                          /* F.group_norm does for a group holding a non-finite value.  nlc_conv2d_stats_partials(desc,          */
                          /* dtype) must be > 0 (16-bit, NHWC, Cout % 128 == 0, the LDS-halo and LDS-DMA kernels).  Consumed by */
                          /* nlc_groupnorm_prestats / _pool2x2 / _coef.                                                        */
-    int32_t policy;      /* NLC_CONV_* (0 = AUTO); the three queries below honour it like nlc_conv2d does */
+    int32_t policy;      /* NLC_CONV_* (0 = AUTO); the queries below honour it like nlc_conv2d does      */
     const float* gn_coef; /* optional (NULL = none): the GroupNorm (+FiLM) (+SiLU) that precedes this convolution in the reference */
     int32_t gn_act;      /* (src/unet_adm.py:182-185,206-211,248-252) applied to the INPUT on its way through LDS instead of in a     */
                          /* separate pass over HBM: logical input = act(a[b][c] * x + b[b][c]) inside the image, 0 in the padding;    */
@@ -219,20 +219,30 @@ typedef struct nlc_conv_desc {
 } nlc_conv_desc;
 
 int nlc_conv2d(const nlc_conv_desc* d, int dtype, void* stream);
-/* bytes of workspace with which nlc_conv2d would split K for this descriptor (0: it would not).  Passing the workspace
+/* nlc_conv2d decides ONCE which of its kernels runs a descriptor - small-map, narrow, LDS-halo (split-K or not), pointwise, LDS-DMA
+ * or generic - from the geometry, the dtype, policy / tuning and whether a sufficient workspace came along, then checks every optional
+ * attachment (stats_out, workspace, gn_coef, norm_out, gn_in) against that decision and launches exactly that kernel.  The five
+ * queries below are views of the same decision (one planner serves them and the launch), taken as if the workspace they size were
+ * passed: they cannot answer for a kernel the launch would not pick.  Each returns 0 for an invalid descriptor or policy
+ * NLC_CONV_GENERIC.
+ *
+ * bytes of workspace with which nlc_conv2d would split K for this descriptor (0: it would not).  Passing the workspace
  * is the caller's opt-in: with none, one summation order is kept (the f32 parity path).  Partial sums are f32 and are
  * added in a fixed order. */
 int64_t nlc_conv2d_workspace_bytes(const nlc_conv_desc* d, int dtype);
-/* 1 if nlc_conv2d would add this launch's GroupNorm statistics to stats_out for this descriptor, 0: it would not */
+/* 1 if the planned kernel adds this launch's GroupNorm statistics to stats_out (16-bit, NHWC, Cout % 128 == 0, every kernel but the
+ * narrow and the generic one), 0: it does not, and a stats_out attached all the same is refused */
 int nlc_conv2d_stats_partials(const nlc_conv_desc* d, int dtype);
-/* 1 if nlc_conv2d would apply desc.gn_coef / gn_act in its LDS prologue for this descriptor (geometry, dtype and policy decide;
- * the gn_* fields themselves are not looked at), else 0: the caller then runs nlc_groupnorm(_prestats) as a separate pass */
+/* the plan of this descriptor WITH a gn_coef (and no norm_out) attached: 1 if its kernel applies gn_coef / gn_act in its LDS prologue
+ * (geometry, dtype and policy decide; the gn_* fields themselves are not looked at), else 0: the caller then runs
+ * nlc_groupnorm(_prestats) as a separate pass.  Also 0 for a launch the narrow kernel takes as it stands, which is left to it. */
 int nlc_conv2d_prologue_supported(const nlc_conv_desc* d, int dtype);
-/* 1 if nlc_conv2d would honour desc->norm_out for this descriptor (norm_out / gn_coef themselves are not looked at), else 0 */
+/* the plan of this descriptor WITH norm_out and gn_coef attached: 1 if its kernel writes norm_out (norm_out / gn_coef themselves are
+ * not looked at), else 0 */
 int nlc_conv2d_norm_out_supported(const nlc_conv_desc* d, int dtype);
-/* 1 if nlc_conv2d would honour desc->gn_in for this descriptor (the small-map 3x3 kernel takes it; gn_in itself is not looked at),
- * else 0: the caller then runs nlc_groupnorm(_prestats) as a separate pass.  nlc_conv2d_workspace_bytes / _stats_partials answer for
- * the kernel that WILL run: set desc->gn_in (or policy NLC_CONV_FORCE_SMALL) before asking them. */
+/* the plan of this descriptor WITH a gn_in attached: 1 if it names the small-map 3x3 kernel, which applies it (gn_in itself is not
+ * looked at), else 0: the caller then runs nlc_groupnorm(_prestats) as a separate pass.  nlc_conv2d_workspace_bytes / _stats_partials
+ * answer for the descriptor as it stands: set desc->gn_in (or policy NLC_CONV_FORCE_SMALL) before asking them. */
 int nlc_conv2d_gn_in_supported(const nlc_conv_desc* d, int dtype);
 
 /* EXPERIMENT, measured and not used by the networks ("One launch per ResBlock"): both 3x3 convolutions of a ResBlock

@@ -76,6 +76,108 @@ def test_argument_validation_without_gpu():
     assert lib.nlc_groupnorm(None, None, 8, 0, 1, 1, 3, 1e-5, None, None, None, None, 0, 0, None, None, 0, None) == -1
 
 
+QUERIES = ("workspace_bytes", "stats_partials", "prologue_supported", "norm_out_supported", "gn_in_supported")
+_HOST_MEM = ctypes.create_string_buffer(64)          # what the descriptors of the query tests point at: the host queries only look at
+_HOST_PTR = (ctypes.addressof(_HOST_MEM) + 15) & ~15     # presence and alignment of a pointer, never through it
+_HOST_GN_IN = None
+
+
+def conv_query_desc(B, H, W, C0, Cout, k=3, *, C1=0, stride=1, dtype="bf16", policy="auto", tuning=0, gn_in=False, bias=True, nchw=False,
+                    ups=False):
+    """(ConvDesc, dtype enum) of a 'same'-padded convolution as ops.conv2d would describe it, for the host queries (no GPU, no tensors)."""
+    from diffusion_nlc_amd import _ext, ops
+    global _HOST_GN_IN
+    kbe = 32 if dtype == "f32" else 64
+    pad = k // 2
+    HL, WL = (2 * H, 2 * W) if ups else (H, W)
+    d = _ext.ConvDesc(x0=_HOST_PTR, x1=_HOST_PTR if C1 else None, C0=C0, C1=C1, B=B, Hin=H, Win=W, Hout=(HL + 2 * pad - k) // stride + 1,
+                      Wout=(WL + 2 * pad - k) // stride + 1, Cout=Cout, KH=k, KW=k, stride=stride, pad_t=pad, pad_l=pad, upsample2x=int(ups),
+                      w=_HOST_PTR, Cin_pad=-(-(C0 + C1) // kbe) * kbe, Cout_pad=-(-Cout // 128) * 128, bias=_HOST_PTR if bias else None,
+                      out_scale=1.0, out=_HOST_PTR, out_mode=ops.OUT_NCHW_F32 if nchw else ops.OUT_NHWC, policy=ops.CONV_POLICIES[policy],
+                      tuning=tuning)
+    if gn_in:
+        if _HOST_GN_IN is None:
+            _HOST_GN_IN = _ext.GnIn(stats0=_HOST_PTR, groups=1)
+        d.gn_in = ctypes.pointer(_HOST_GN_IN)
+    return d, {"f32": _ext.NLC_F32, "bf16": _ext.NLC_BF16, "f16": _ext.NLC_F16}[dtype]
+
+
+def conv_queries(lib, d, dt):
+    return {q: int(getattr(lib, "nlc_conv2d_" + q)(ctypes.byref(d), dt)) for q in QUERIES}
+
+
+# (B, H, W, C0, Cout, k) + options: the levels of the three networks and the shapes around every threshold of the dispatch
+# (64 narrow patches, 128 halo tiles, split-K below 256, 768 pointwise tiles, the small-map geometries)
+QUERY_SHAPES = [
+    (2, 8, 8, 64, 128, 3), (2, 8, 8, 128, 128, 3), (16, 8, 8, 1024, 1024, 3), (8, 16, 16, 512, 512, 3), (8, 32, 32, 256, 256, 3),
+    (200, 8, 8, 256, 256, 3), (16, 8, 8, 1024, 1024, 3, dict(C1=512)), (3, 8, 8, 192, 128, 3), (1, 8, 8, 64, 128, 3),
+    (1, 16, 16, 64, 128, 3), (2, 64, 64, 1024, 128, 3), (16, 16, 16, 1024, 1024, 3), (16, 16, 16, 1024, 512, 3), (16, 32, 32, 512, 512, 3),
+    (1, 128, 128, 64, 128, 3), (1, 256, 256, 128, 256, 3), (2, 64, 64, 256, 256, 3, dict(ups=True)), (2, 16, 16, 64, 200, 3),
+    (4, 64, 64, 64, 6, 3), (3, 64, 64, 64, 6, 3), (16, 256, 256, 256, 6, 3), (1, 32, 32, 128, 3, 3), (4, 64, 64, 64, 16, 3, dict(nchw=True)),
+    (12, 64, 64, 64, 256, 1), (11, 64, 64, 64, 256, 1), (16, 128, 128, 256, 256, 1), (16, 64, 64, 512, 256, 1, dict(C1=256)),
+    (16, 8, 8, 1024, 3072, 1), (2, 4, 4, 1024, 256, 1), (200, 16, 16, 256, 512, 1),
+    (2, 16, 16, 64, 64, 3, dict(stride=2)), (1, 8, 8, 128, 128, 3, dict(stride=2)), (16, 64, 64, 256, 256, 3, dict(stride=2)),
+    (1, 8, 8, 64, 16, 5), (2, 16, 16, 64, 128, 5), (2, 9, 7, 32, 6, 3), (2, 8, 8, 96, 200, 3, dict(bias=False)),
+]
+
+
+def _query_cases():
+    for s in QUERY_SHAPES:
+        kw = dict(s[6]) if len(s) > 6 else {}
+        for dtype in ("bf16", "f16", "f32"):
+            yield s[:6], dict(kw, dtype=dtype)
+
+
+def test_conv_queries_are_views_of_one_plan():
+    """nlc_conv2d's dispatch is planned once (conv_igemm.hip: plan_conv) and the five host queries return fields of that plan.  What
+    follows from that, over the networks' levels and the shapes around every threshold, in all three dtypes - on the host (the
+    library answers the queries without a GPU):
+      * policy "generic": every query 0;
+      * where gn_in is supported, asking with gn_in set or under policy "small" plans the small-map kernel: statistics iff
+        Cout % 128 == 0, the same workspace either way (the small-map kernel's: a function of its k-slices alone), and the prologue
+        query - which never looks at the attachments - unchanged;
+      * norm_out supported => no workspace (the pointwise kernel never splits K);
+      * a <= 16-channel 3x3 that the narrow kernel takes (policy "auto", >= 64 patches) has neither statistics nor a workspace;
+      * tuning bit 11 (no split-K in the halo and fast kernels) => no workspace, for every launch that is not a small-map one (whose
+        k-slices are part of its geometry, not a policy)."""
+    from diffusion_nlc_amd import _ext
+    lib = _ext.load()
+    seen = {q: set() for q in QUERIES}
+    for shape, kw in _query_cases():
+        B, H, W, C0, Cout, k = shape
+        base = conv_queries(lib, *conv_query_desc(*shape, **kw))
+        for q in QUERIES:
+            seen[q].add(base[q] > 0)
+        for policy in ("auto", "halo", "no_halo", "small"):
+            got = conv_queries(lib, *conv_query_desc(*shape, policy=policy, **kw))
+            assert got["stats_partials"] in (0, 1) and got["workspace_bytes"] >= 0
+            if got["stats_partials"]:
+                assert kw["dtype"] != "f32" and Cout % 128 == 0 and not kw.get("nchw"), (shape, kw, policy)
+            if got["norm_out_supported"]:
+                assert got["workspace_bytes"] == 0, (shape, kw, policy)
+        assert not any(conv_queries(lib, *conv_query_desc(*shape, policy="generic", **kw)).values()), (shape, kw)
+        assert not any(conv_queries(lib, *conv_query_desc(*shape, policy="generic", gn_in=True, **kw)).values()), (shape, kw)
+        if base["gn_in_supported"]:
+            with_gn = conv_queries(lib, *conv_query_desc(*shape, gn_in=True, **kw))
+            as_small = conv_queries(lib, *conv_query_desc(*shape, policy="small", **kw))
+            for got in (with_gn, as_small):
+                assert got["gn_in_supported"] == 1
+                assert got["stats_partials"] == (1 if Cout % 128 == 0 else 0), (shape, kw)
+                assert got["prologue_supported"] == base["prologue_supported"], (shape, kw)
+            assert with_gn["workspace_bytes"] == as_small["workspace_bytes"], (shape, kw)
+            slices = (with_gn["workspace_bytes"] - 4096) // (B * H * W * Cout * 4) if with_gn["workspace_bytes"] else 1
+            assert 1 <= slices <= 8 and with_gn["workspace_bytes"] == (slices * B * H * W * Cout * 4 + 4096 if slices > 1 else 0), (shape, kw)
+            assert conv_queries(lib, *conv_query_desc(*shape, gn_in=True, tuning=1 << 21, **kw))["gn_in_supported"] == 0
+        else:
+            assert conv_queries(lib, *conv_query_desc(*shape, gn_in=True, **kw))["gn_in_supported"] == 0
+        if k == 3 and Cout <= 16 and kw["dtype"] != "f32" and kw.get("stride", 1) == 1 and H % 16 == 0 and W % 16 == 0 and B * (H // 16) * (W // 16) >= 64:
+            assert base["stats_partials"] == 0 and base["workspace_bytes"] == 0 and base["prologue_supported"] == 0, (shape, kw)
+        for policy in ("auto", "halo", "no_halo"):
+            assert conv_queries(lib, *conv_query_desc(*shape, policy=policy, tuning=1 << 11, **kw))["workspace_bytes"] == 0, (shape, kw, policy)
+    for q in QUERIES:          # the shapes reach both answers of every query
+        assert seen[q] == {False, True}, q
+
+
 def test_no_cpu_fallback():
     from diffusion_nlc_amd._ext import NlcError
     eps, sig, _ = build_product("adm_tiny_b")

@@ -1525,3 +1525,78 @@ def test_one_launch_resblock_equals_its_two_fused_launches(shape, t16):
     assert torch.equal(got, want)
     assert torch.equal(ops.ride_stats(got), ops.ride_stats(want))
     assert int(ops._RB_BARRIER[x.device].abs().sum()) == 0
+
+
+# One case per kernel that nlc_conv2d's planner (conv_igemm.hip: plan_conv) can name: the smallest descriptor for which it names that
+# kernel, found by scanning the host queries over B x map x channels x policy on the CPU (the launch reports the kernel it reaches).
+# (kernel, dtype, policy, (B, Cin, H, W, Cout, k, stride), statistics ride along, split-K workspace)
+PLANNED_KERNEL_CASES = [
+    ("small", torch.bfloat16, "small", (2, 64, 8, 8, 128, 3, 1), True, False),             # 128 pixels in all: one tile
+    ("small-splitk", torch.bfloat16, "small", (2, 128, 8, 8, 128, 3, 1), True, True),      # two k-slices of one 64-channel block
+    ("narrow", torch.bfloat16, "auto", (4, 64, 64, 64, 6, 3, 1), False, False),            # its floor of 64 patches
+    ("halo-splitk", torch.bfloat16, "auto", (2, 1024, 64, 64, 128, 3, 1), True, True),     # 32 tiles x 4 slices of 4 channel blocks
+    ("halo", torch.bfloat16, "halo", (1, 64, 16, 16, 128, 3, 1), True, False),             # one tile, forced
+    ("halo", torch.float32, "halo", (1, 64, 16, 16, 128, 3, 1), False, False),
+    ("pointwise", torch.bfloat16, "auto", (12, 64, 64, 64, 256, 1, 1), True, False),       # its floor of 768 tiles
+    ("fast", torch.bfloat16, "auto", (1, 64, 8, 8, 128, 3, 2), True, False),               # stride 2: one channel block, nothing to split
+    ("fast-splitk", torch.bfloat16, "auto", (1, 128, 8, 8, 128, 3, 2), True, True),
+    ("fast", torch.float32, "auto", (1, 32, 8, 8, 128, 3, 2), False, False),
+    ("fast-splitk", torch.float32, "auto", (1, 64, 8, 8, 128, 3, 2), False, True),
+    ("generic", torch.bfloat16, "auto", (1, 64, 8, 8, 16, 5, 1), False, False),
+    ("generic", torch.float32, "auto", (1, 64, 8, 8, 16, 5, 1), False, False),
+]
+
+
+@pytest.mark.parametrize("case", PLANNED_KERNEL_CASES, ids=lambda c: f"{c[0]}-{DTYPE_IDS[DTYPES.index(c[1])]}")
+def test_conv2d_launch_agrees_with_its_queries(case):
+    """Query <=> launch, once per planned kernel.  The descriptor gets stats_out exactly when nlc_conv2d_stats_partials > 0 and a
+    workspace of exactly nlc_conv2d_workspace_bytes (ops.conv2d attaches both from the queries; the workspace size is cut to the
+    byte here): the launch is accepted, matches F.conv2d in f32 on the rounded operands at this file's tolerance for the dtype, and
+    the totals describe the stored output.  Where the query says no statistics, a stats_out attached all the same is refused
+    (NLC_EINVAL) and nothing is launched."""
+    import ctypes
+    from diffusion_nlc_amd import _ext, ops
+    kernel, dtype, policy, (B, Cin, H, W, Cout, k, stride), want_stats, want_ws = case
+    g = torch.Generator().manual_seed(_seed(case[:1] + case[3:]))
+    x = torch.randn(B, Cin, H, W, generator=g)
+    w = torch.randn(Cout, Cin, k, k, generator=g) / math.sqrt(Cin * k * k)
+    b = torch.randn(Cout, generator=g) * 0.1
+    ref = F.conv2d(_rt(x, dtype), _rt(w, dtype), b, stride=stride, padding=k // 2).permute(0, 2, 3, 1)
+    pw = ops.pack_conv(w, b, dtype, _dev())
+    lib = _ext.load()
+    old = ops.CONV_POLICY
+    ops.CONV_POLICY = policy
+    try:
+        d, out, keep = ops.conv2d(_nhwc(x, dtype), pw, stride=stride, allow_split=True, desc_only=True)
+    finally:
+        ops.CONV_POLICY = old
+    dt = ops.dtype_enum(dtype)
+    stats_q, need = lib.nlc_conv2d_stats_partials(ctypes.byref(d), dt), lib.nlc_conv2d_workspace_bytes(ctypes.byref(d), dt)
+    print(f"{kernel}: stats_partials {stats_q}, workspace_bytes {need}")
+    assert (stats_q > 0) == want_stats and (need > 0) == want_ws, "the planner no longer names this kernel for this descriptor"
+    st = ops.ride_stats(out)
+    assert (st is not None) == want_stats and bool(d.stats_out) == want_stats
+    assert bool(d.workspace) == want_ws and d.workspace_bytes >= need
+    d.workspace_bytes = need
+    out.fill_(float("nan"))
+    if not want_stats:                               # refused before anything is launched: the output keeps its fill
+        bogus = torch.zeros(B * (Cout // 4 + 1) * 4 + 2, device=_dev(), dtype=torch.int64)
+        d.stats_out, d.stats_bytes = (bogus.data_ptr() + 15) & ~15, B * (Cout // 4 + 1) * 32
+        assert lib.nlc_conv2d(ctypes.byref(d), dt, ops._stream()) == _ext.NLC_EINVAL
+        assert b"does not emit statistics" in lib.nlc_last_error()
+        torch.cuda.synchronize()
+        assert bool(torch.isnan(out.float()).all()) and int(bogus.abs().sum()) == 0
+        d.stats_out, d.stats_bytes = None, 0
+    rc = lib.nlc_conv2d(ctypes.byref(d), dt, ops._stream())
+    assert rc == 0, lib.nlc_last_error()
+    torch.cuda.synchronize()
+    _close(out, ref, _tol(dtype), f"conv2d ({kernel})")
+    if want_stats:
+        gran = Cout // st.shape[1]
+        ch = out.float().cpu().view(B, -1, Cout // gran, gran).double()
+        tot = _totals(st)
+        rs, rq = ch.sum(dim=(1, 3)), (ch ** 2).sum(dim=(1, 3))
+        assert (tot[..., 0] - rs).abs().max() <= 2e-3 * rs.abs().max().clamp(min=1.0)
+        assert ((tot[..., 1] - rq) / rq).abs().max() < 2e-3
+    if want_ws:                                      # (every split launch leaves the arrival counters zero)
+        assert int(ops._conv_workspace(_dev(), need)[:1024].view(torch.int32).abs().sum()) == 0
