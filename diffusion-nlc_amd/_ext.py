@@ -15,7 +15,7 @@ _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("NLC_HIP_LIB", _HERE / "libnlc_hip.so"))     # override: kernel A/B experiments only
 BUILD_SCRIPT = _HERE / "csrc" / "build.sh"
 
-ABI_VERSION = 7                 # NLC_ABI_VERSION of include/nlc_hip.h
+ABI_VERSION = 8                 # NLC_ABI_VERSION of include/nlc_hip.h
 NLC_F32, NLC_BF16, NLC_F16 = 0, 1, 2
 MATH_NATIVE, MATH_F16X3 = 0, 1      # nlc_conv_desc.math / nlc_pack_conv_weights_ex
 ACT_NONE, ACT_SILU, ACT_GELU = 0, 1, 2
@@ -26,6 +26,7 @@ SCHED_VARIANTS = {
 }
 CLIP_MODES = {"none": 0, "clamp": 1, "dynamic": 2}
 VAR_MODES = {"none": 0, "fixedsmall": 1, "fixedlarge": 2, "learned": 3}
+GROUP_BLOCK, GROUP_CHANNEL = 0, 1   # nlc_group_desc.mode
 
 
 class NlcError(RuntimeError):
@@ -117,6 +118,16 @@ class SigmaDesc(C.Structure):
     ]
 
 
+class GroupDesc(C.Structure):
+    """nlc_group_desc: passed BY VALUE to nlc_group_A / nlc_group_Apinv / nlc_group_project."""
+    _fields_ = [
+        ("mode", C.c_int32),
+        ("B", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+        ("r", C.c_int32),
+        ("w", C.c_float * 64), ("p", C.c_float * 64),
+    ]
+
+
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
 # name -> (restype, argtypes); every symbol include/nlc_hip.h declares
@@ -167,6 +178,9 @@ SIGNATURES = {
     "nlc_f64_lincomb": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _vp]),
     "nlc_inpaint_A": (C.c_int, [_vp, _vp, _vp, _i, _i, _i64, _i64, _vp]),
     "nlc_inpaint_Apinv": (C.c_int, [_vp, _vp, _vp, _i, _i, _i64, _i64, _vp]),
+    "nlc_group_A": (C.c_int, [_vp, GroupDesc, _vp, _vp]),
+    "nlc_group_Apinv": (C.c_int, [_vp, GroupDesc, _vp, _vp]),
+    "nlc_group_project": (C.c_int, [_vp, _vp, GroupDesc, _vp]),
 }
 
 _lib = None

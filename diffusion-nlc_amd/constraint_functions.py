@@ -1,12 +1,21 @@
-"""Inpainting constraint for restoration sampling (BASELINE config 4).
+"""Measurement operators for restoration sampling: inpainting (BASELINE config 4), average-pooling
+super-resolution and colorization.
 
-Mirrors the parts of the reference that the inpainting path touches:
-``functions/svd_operators.py:324-359`` (``Inpainting.A`` / ``A_pinv``), ``src/constraint_functions.py:216-241``
-(the ``svd_constraint`` inpainting branch) and ``image_sample.py:282-343,371-383`` (``Constraint_Function`` with the
-``affine_svd`` projection  x0 <- x0 - A^+(A x0 - y)).  For inpainting that projection is "copy the known
-pixels": the per-step work is fused into ``nlc_sched_step`` (mask / known), A and A^+ themselves are the two
-gather kernels of ``csrc/constraint.hip``.  The other degradations of the reference (SR, deblurring,
-colorisation, compressed sensing, DDRM) are out of scope (not in BASELINE's configs).
+Mirrors the parts of the reference that these paths touch: ``functions/svd_operators.py:324-359`` (``Inpainting``),
+``:479-533`` (``SuperResolution``), ``:627-667`` (``Colorization``), ``src/constraint_functions.py:216-251`` (the
+``svd_constraint`` branches) and ``image_sample.py:282-343,371-383`` (``Constraint_Function`` with the ``affine_svd``
+projection  x0 <- x0 - A^+(A x0 - y)).
+
+* Inpainting: the projection is "copy the known pixels"; the per-step work is fused into ``nlc_sched_step`` (mask /
+  known), A and A^+ themselves are the two gather kernels of ``csrc/constraint.hip``.
+* Super-resolution and colorization are "one weighted sum per group of n entries" (an r x r block, or the 3 channels of
+  a pixel).  With the weights w and p_i = w_i / sum w^2:  A(x)[g] = sum_i w_i x_i,  A^+(y)[i of g] = p_i y[g],  and the
+  projection is  x0_i + p_i (y[g] - sum_j w_j x0_j):  the three kernels of ``csrc/restore.hip``.  Per step the loop
+  runs clip / ``nlc_group_project`` / x_prev (three launches; the projection needs a per-group reduction that the
+  element-wise scheduler kernel does not have).
+
+The other degradations of the reference (bicubic SR, deblurring, compressed sensing, denoising), the ``*_gd`` /
+``simple`` projections and ``ddrm`` with the group-sum operators raise NotImplementedError.
 """
 from __future__ import annotations
 
@@ -72,10 +81,128 @@ class Inpainting:
     At = A_pinv          # singular values are all 1: A^T = A^+
 
 
+def group_tables(weights):
+    """(w, p) of a group-sum operator as the kernels take them: p_i = w_i / sum_j w_j^2 in float64, each table rounded to
+    float32 once.  The mean (w_i = 1/n) has p_i = 1: passed as 1.0f exactly, whatever 1/n rounds to."""
+    w = np.asarray(weights, dtype=np.float64).reshape(-1)
+    if w.size < 1 or w.size > 64:
+        raise NlcError(f"group of {w.size} entries: 1..64 are supported")
+    is_mean = bool(np.all(w == w[0])) and abs(w[0] * w.size - 1.0) < 1e-12
+    p = np.ones_like(w) if is_mean else w / np.sum(w * w)
+    return w.astype(np.float32), p.astype(np.float32)
+
+
+def group_desc(mode, B, C, H, W, r, w, p):
+    d = _ext.GroupDesc(mode=mode, B=B, C=C, H=H, W=W, r=r)
+    for i, (wi, pi) in enumerate(zip(w, p)):
+        d.w[i], d.p[i] = float(wi), float(pi)
+    return d
+
+
+def group_A(x, desc):
+    """y = A x.  ``x``: contiguous f32 [B][C][H][W] on the current device; returns (B, groups per sample)."""
+    B = desc.B
+    n = (desc.C * (desc.H // max(desc.r, 1)) * (desc.W // max(desc.r, 1))) if desc.mode == _ext.GROUP_BLOCK else desc.H * desc.W
+    out = torch.empty(B, n, device=x.device, dtype=torch.float32)
+    check(_ext.load().nlc_group_A(x.data_ptr(), desc, out.data_ptr(), _s()), "nlc_group_A")
+    return out
+
+
+def group_Apinv(y, desc):
+    """x = A^+ y (or A^T y with w in the place of p).  Returns (B, C*H*W)."""
+    out = torch.empty(desc.B, desc.C * desc.H * desc.W, device=y.device, dtype=torch.float32)
+    check(_ext.load().nlc_group_Apinv(y.data_ptr(), desc, out.data_ptr(), _s()), "nlc_group_Apinv")
+    return out
+
+
+def group_project_(x0, y, desc):
+    """x0 <- x0 + p (y - A x0), in place, one launch."""
+    check(_ext.load().nlc_group_project(x0.data_ptr(), y.data_ptr(), desc, _s()), "nlc_group_project")
+    return x0
+
+
+class _GroupSum:
+    """An operator with one weighted sum per group (csrc/restore.hip).  Subclasses set mode / channels / img_dim / ratio and
+    the weights of one group."""
+
+    def _setup(self, mode, channels, img_dim, ratio, weights, device):
+        self.mode, self.channels, self.img_dim, self.ratio = mode, channels, img_dim, ratio
+        self.device = torch.device(device)
+        self.w, self.p = group_tables(weights)
+        self.groups = channels * (img_dim // ratio) ** 2 if mode == _ext.GROUP_BLOCK else img_dim ** 2
+        self._singular = float(np.float32(np.sqrt(np.sum(self.w.astype(np.float64) ** 2))))
+
+    def desc(self, B, transpose=False):
+        return group_desc(self.mode, B, self.channels, self.img_dim, self.img_dim, self.ratio, self.w, self.w if transpose else self.p)
+
+    def singulars(self):
+        return torch.full((self.groups,), self._singular, device=self.device)
+
+    @ops.on_device
+    def A(self, vec):
+        x = vec.reshape(vec.shape[0], -1).to(self.device, torch.float32).contiguous()
+        if x.shape[1] != self.channels * self.img_dim ** 2:
+            raise ValueError("A: vector length mismatch")
+        return group_A(x, self.desc(x.shape[0]))
+
+    def _back(self, vec, transpose):
+        y = vec.reshape(vec.shape[0], -1).to(self.device, torch.float32).contiguous()
+        if y.shape[1] != self.groups:
+            raise ValueError("A_pinv: measurement length mismatch")
+        return group_Apinv(y, self.desc(y.shape[0], transpose))
+
+    @ops.on_device
+    def A_pinv(self, vec):
+        return self._back(vec, False)
+
+    @ops.on_device
+    def At(self, vec):
+        return self._back(vec, True)
+
+    @ops.on_device
+    def project_(self, x0, y):
+        """x0 <- x0 - A^+(A x0 - y) in place.  ``x0``: contiguous f32 (B, C, H, W) on this device; ``y``: contiguous f32 (B, groups)."""
+        if not (x0.is_contiguous() and x0.dtype == torch.float32 and x0.device == y.device and x0.is_cuda):
+            raise NlcError("project_: x0 must be a contiguous float32 tensor on the operator's device")
+        if x0.numel() != x0.shape[0] * self.channels * self.img_dim ** 2 or y.numel() != x0.shape[0] * self.groups:
+            raise NlcError("project_: shape mismatch")
+        return group_project_(x0, y, self.desc(x0.shape[0]))
+
+
+class SuperResolution(_GroupSum):
+    """functions/svd_operators.py:479-533: the mean of every ratio x ratio block; y is (B, C * (img_dim/ratio)^2), channel-major."""
+
+    def __init__(self, channels, img_dim, ratio, device):
+        ratio = int(ratio)
+        if not 1 <= ratio <= 8:
+            raise NlcError(f"SuperResolution: ratio {ratio} outside 1..8")
+        if img_dim % ratio != 0:
+            raise NlcError(f"SuperResolution: img_dim {img_dim} is not a multiple of ratio {ratio}")
+        self.y_dim = img_dim // ratio
+        self._setup(_ext.GROUP_BLOCK, channels, img_dim, ratio, [1.0 / ratio ** 2] * ratio ** 2, device)
+
+
+class Colorization(_GroupSum):
+    """functions/svd_operators.py:627-667: grey = 0.3333 R + 0.3334 G + 0.3333 B (the reference's literal weights); y is (B, H*W)."""
+
+    WEIGHTS = (0.3333, 0.3334, 0.3333)
+
+    def __init__(self, img_dim, device):
+        self._setup(_ext.GROUP_CHANNEL, 3, img_dim, 1, self.WEIGHTS, device)
+
+
+GROUP_SUM_CONSTRAINTS = ("sr_averagepooling", "colorization")
+
+
 def svd_constraint(fn, fn_scale=4, device="cuda:0", base_mask_dir="store/inp_masks", image_size=256, channels=3):
-    """src/constraint_functions.py:206-241, inpainting branch only."""
+    """src/constraint_functions.py:206-251: the inpainting, ``sr_averagepooling`` and ``colorization`` branches."""
+    if fn == "sr_averagepooling":
+        return SuperResolution(channels, image_size, int(fn_scale), device)
+    if fn == "colorization":
+        return Colorization(image_size, device)
     if "inpainting" not in fn:
-        raise NotImplementedError(f"constraint '{fn}': only the inpainting operators are on the HIP path (SURVEY.md §8 f-1)")
+        raise NotImplementedError(f"constraint '{fn}': only the inpainting, sr_averagepooling and colorization operators are on the "
+                                  f"HIP path (SURVEY.md §8 f-1)")
     if fn == "inpainting_random":
         missing_r = torch.randperm(image_size ** 2)[: image_size ** 2 // 2].long() * 3
     elif fn in ("inpainting_ddnm", "inpainting_half"):
@@ -104,11 +231,28 @@ class AffineInpaint:
         return x0_t - Ap(A(flat) - self.y.reshape(self.y.size(0), -1)).reshape(*x0_t.size())
 
 
-class Constraint_Function:
-    """image_sample.py:282-343 for deg='inpainting*' / proj='svd'."""
+class AffineGroup:
+    """``partial(affine_svd, A=A, Ap=Ap, y=y)`` (image_sample.py:376-381) for a group-sum operator.  ``project_`` is what the
+    sampling loop calls: one ``nlc_group_project`` launch, in place.  Calling the object gives the reference-shaped composition."""
 
-    def __init__(self, deg, A_funcs: Inpainting, channels=3, image_size=256, lr=1.0):
-        if "inp" not in deg:
+    def __init__(self, op: _GroupSum, y: torch.Tensor, shape):
+        self.op = op
+        self.shape = tuple(shape)
+        self.y = y.reshape(y.shape[0], -1).to(op.device, torch.float32).contiguous()
+
+    def project_(self, x0):
+        return self.op.project_(x0, self.y)
+
+    def __call__(self, x0_t):
+        A, Ap = self.op.A, self.op.A_pinv
+        return x0_t - Ap(A(x0_t.reshape(x0_t.size(0), -1)) - self.y).reshape(*x0_t.size())
+
+
+class Constraint_Function:
+    """image_sample.py:282-343 for deg='inpainting*' / 'sr_averagepooling' / 'colorization' and proj='svd'."""
+
+    def __init__(self, deg, A_funcs, channels=3, image_size=256, lr=1.0):
+        if "inp" not in deg and deg not in GROUP_SUM_CONSTRAINTS:
             raise NotImplementedError(deg)
         self.deg, self.op = deg, A_funcs
         self.A, self.Ap = A_funcs.A, A_funcs.A_pinv
@@ -118,16 +262,22 @@ class Constraint_Function:
         return self.A(x)
 
     def inv_transform(self, y):
+        if self.deg == "colorization":               # image_sample.py:319-320: the grey image on all three channels, not A^+ y
+            return y.view(y.shape[0], 1, self.image_size, self.image_size).repeat(1, 3, 1, 1)
         Apy = self.Ap(y).view(y.shape[0], self.channels, self.image_size, self.image_size)
         if self.deg == "inpainting":                 # image_sample.py:321-322
             Apy = Apy + self.Ap(self.A(torch.ones_like(Apy))).reshape(*Apy.shape) - 1
         return Apy
 
     def constraint_fn(self, x0_t, y, lambda_t=None):
+        if isinstance(self.op, _GroupSum):
+            return AffineGroup(self.op, y, x0_t.shape)(x0_t)
         return AffineInpaint(self.op, y, x0_t.shape)(x0_t)
 
-    def bind(self, y, shape) -> AffineInpaint:
+    def bind(self, y, shape):
         """The per-batch projection (what evaluate_constraint builds with functools.partial, image_sample.py:648)."""
+        if isinstance(self.op, _GroupSum):
+            return AffineGroup(self.op, y, shape)
         return AffineInpaint(self.op, y, shape)
 
     def loss(self, x, y):

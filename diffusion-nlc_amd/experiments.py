@@ -298,6 +298,15 @@ class ExperimentDiffusion:
             d.mask, d.known = constrain_fn.mask_chw.data_ptr(), constrain_fn.known.data_ptr()
             ops.sched_step(d, st["nan"])
             x0_hat = x0
+        elif use_constraint and not return_log and hasattr(constrain_fn, "project_"):
+            # group-sum operators (super-resolution, colorization): the projection needs a reduction over each group, which the
+            # element-wise scheduler kernel does not have - clip, project x0 in place (one launch), x_prev
+            d.phases = 1
+            ops.sched_step(d)
+            constrain_fn.project_(x0)
+            x0_hat = x0
+            d.phases = 2
+            ops.sched_step(d, st["nan"])
         elif use_constraint or (return_log and constrain_fn is not None):
             d.phases = 1                                   # clip only
             ops.sched_step(d)

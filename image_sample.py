@@ -12,8 +12,10 @@ diffusion-nlc_amd/.  Differences, all on side effects the reference hard-codes:
   ``--return_log`` (default 0): the 2.5 GB-per-batch history is only copied to the host when asked for.
 * ``--synthetic NAME`` (extension): run without ``store/`` / ``results/`` files, with a built-in model
   configuration and the deterministic filler weights (the reference ships neither configs nor checkpoints).
-* ``--constraint``: the inpainting operators (``inpainting``, ``inpainting_half``) with ``--constraint_proj svd``
-  run on the HIP path; the other SVD operators and the GD projections raise NotImplementedError.
+* ``--constraint``: the inpainting operators (``inpainting``, ``inpainting_half``), ``sr_averagepooling`` (block mean,
+  ``--constraint_scale`` = the ratio, 1..8) and ``colorization`` with ``--constraint_proj svd`` run on the HIP path
+  (SURVEY §8 f-1); the other SVD operators and the GD projections raise NotImplementedError, and so does
+  ``--constraint_proj ddrm`` with anything but inpainting.
   With ``--synthetic`` the validation images are seeded U(0,1) tensors and the mask is the seeded random 50 %
   of pixels of BASELINE config 4 (no dataset / ``store/inp_masks`` files ship with the reference).
 """
@@ -303,8 +305,12 @@ def projection_loop(self, *args, **kwargs):
 
 def get_constraint_function(args, image_size, channels):
     """image_sample.py:359-405 for the operators on the HIP path: inpainting with the 'svd' (or 'ddrm', same
-    operator) projection."""
-    from src.constraint_functions import Constraint_Function, svd_constraint
+    operator) projection; average-pooling super-resolution and colorization with 'svd'."""
+    from src.constraint_functions import GROUP_SUM_CONSTRAINTS, Constraint_Function, svd_constraint
+    if args.constraint_proj == "ddrm" and args.constraint in GROUP_SUM_CONSTRAINTS:
+        raise NotImplementedError(f"--constraint {args.constraint} --constraint_proj ddrm: the reference switches to the operators of "
+                                  "functions/svd_replacement.py there, which have not been checked against the closed forms of "
+                                  "the HIP path; use --constraint_proj svd")
     proj = "svd" if args.constraint_proj == "ddrm" else args.constraint_proj
     if proj != "svd":
         raise NotImplementedError(f"--constraint_proj {args.constraint_proj}: only 'svd' / 'ddrm' are on the HIP path")

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define NLC_ABI_VERSION 7
+#define NLC_ABI_VERSION 8
 
 enum { NLC_F32 = 0, NLC_BF16 = 1, NLC_F16 = 2 };
 /* matrix arithmetic of nlc_conv2d on NLC_F32 tensors (nlc_conv_desc.math; weights must be packed for the same mode):
@@ -510,6 +510,33 @@ int nlc_inpaint_A(const float* x, const int64_t* kept, float* out, int B, int C,
                   int64_t nk, void* stream);
 int nlc_inpaint_Apinv(const float* y, const int32_t* inv, float* out, int B, int C, int64_t HW,
                       int64_t nk, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Group-sum measurement operators on the NCHW f32 state: average-pooling super-resolution
+ * (functions/svd_operators.py:479-533, SuperResolution) and colorization (:627-667, Colorization), which the
+ * reference reaches through V / Vt / U / Ut / add_zeros (:52-80).  Both are one weighted sum per group of n entries;
+ * with the group's weights w and p_i = w_i / sum_j w_j^2:
+ *   nlc_group_A       : y[group]   = sum_i w[i] * x_i             i = 0 .. n-1 in order, products and sums rounded separately
+ *   nlc_group_Apinv   : x_i        = p[i] * y[group]
+ *   nlc_group_project : x0_i      <- x0_i + p[i] * (y[group] - sum_j w[j] * x0_j)     in place, one read and one write of x0:
+ *                       x0 - A^+(A x0 - y), affine_svd, image_sample.py:376-380
+ * NLC_GROUP_BLOCK   : a group is an r x r spatial block of one channel (n = r*r, i row-major inside the block);
+ *                     y is [B][C][H/r][W/r] (SuperResolution.Vt, :505-518).  H % r == W % r == 0, 1 <= r <= 8.
+ * NLC_GROUP_CHANNEL : a group is the 3 channels of one pixel (n = 3, i = channel); y is [B][H*W] (Colorization.Vt, :645-652).
+ * The descriptor is passed by value and carries both tables: the host computes them in double and rounds once
+ * (uniform weights: p[i] = 1.0f exactly).  Passing w in the place of p makes nlc_group_Apinv the transpose A^T.
+ * ---------------------------------------------------------------------------------- */
+enum { NLC_GROUP_BLOCK = 0, NLC_GROUP_CHANNEL = 1 };
+typedef struct nlc_group_desc {
+    int32_t mode;
+    int32_t B, C, H, W;           /* B <= 65535 ; NLC_GROUP_CHANNEL: C == 3 */
+    int32_t r;                    /* block edge, 1..8 (NLC_GROUP_CHANNEL: ignored beyond that range check) */
+    float w[64];                  /* the first n entries are used */
+    float p[64];
+} nlc_group_desc;
+int nlc_group_A(const float* x, nlc_group_desc desc, float* y_out, void* stream);
+int nlc_group_Apinv(const float* y, nlc_group_desc desc, float* x_out, void* stream);
+int nlc_group_project(float* x0, const float* y, nlc_group_desc desc, void* stream);
 
 #ifdef __cplusplus
 }

@@ -5,3 +5,6 @@ from diffusion_nlc_amd import constraint_functions as _impl
 svd_constraint = _impl.svd_constraint
 Constraint_Function = _impl.Constraint_Function
 Inpainting = _impl.Inpainting
+SuperResolution = _impl.SuperResolution
+Colorization = _impl.Colorization
+GROUP_SUM_CONSTRAINTS = _impl.GROUP_SUM_CONSTRAINTS
