@@ -15,7 +15,7 @@ _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("NLC_HIP_LIB", _HERE / "libnlc_hip.so"))     # override: kernel A/B experiments only
 BUILD_SCRIPT = _HERE / "csrc" / "build.sh"
 
-ABI_VERSION = 8                 # NLC_ABI_VERSION of include/nlc_hip.h
+ABI_VERSION = 9                 # NLC_ABI_VERSION of include/nlc_hip.h
 NLC_F32, NLC_BF16, NLC_F16 = 0, 1, 2
 MATH_NATIVE, MATH_F16X3 = 0, 1      # nlc_conv_desc.math / nlc_pack_conv_weights_ex
 ACT_NONE, ACT_SILU, ACT_GELU = 0, 1, 2
@@ -149,6 +149,7 @@ SIGNATURES = {
     "nlc_conv_first_stats_partials": (C.c_int, [_i, _i, _i, _i, _i, _i, _i]),
     "nlc_groupnorm_workspace_bytes": (C.c_int64, [_i, _i, _i, _i]),
     "nlc_groupnorm": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp]),
+    "nlc_groupnorm_totals_supported": (C.c_int, [_i, _i, _i, _i, _i]),
     "nlc_groupnorm_prestats": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp]),
     "nlc_groupnorm_pool2x2": (C.c_int, [_vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp]),
     "nlc_attention": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),

@@ -26,6 +26,13 @@ void nlc_set_error(const char* fmt, ...);
         }                                                        \
     } while (0)
 
+// a validation step that has already set the error: pass its code on
+#define NLC_TRY(call)                                            \
+    do {                                                         \
+        const int rc__ = (call);                                 \
+        if (rc__ != NLC_OK) return rc__;                         \
+    } while (0)
+
 #define NLC_CHECK_LAUNCH(name)                                                    \
     do {                                                                          \
         hipError_t e__ = hipGetLastError();                                       \

@@ -403,19 +403,12 @@ extern "C" int nlc_conv2d_prologue_supported(const nlc_conv_desc* d, int dtype) 
 
 // nlc_gn_in -> the kernel's view (validated)
 static int fill_gn_in(const nlc_gn_in* q, const KParams& p, GnIn& g) {
-    const int g0 = q->granule0 == 4 ? 4 : 8, g1 = q->granule1 == 4 ? 4 : 8;
-    NLC_REQUIRE((q->granule0 == 0 || q->granule0 == 4 || q->granule0 == 8) && (q->granule1 == 0 || q->granule1 == 4 || q->granule1 == 8),
-                "nlc_conv2d: gn_in granules must be 0 (= 8), 4 or 8");
-    NLC_REQUIRE(q->stats0 && (p.C1 == 0) == (q->stats1 == nullptr), "nlc_conv2d: gn_in stats0 / stats1 must match x0 / x1");
-    NLC_REQUIRE(q->groups > 0 && p.Ctot % q->groups == 0, "nlc_conv2d: gn_in groups=%d must divide C0+C1=%d", q->groups, p.Ctot);
-    const int gs = p.Ctot / q->groups;
-    NLC_REQUIRE(gs % g0 == 0 && (p.C1 == 0 || gs % g1 == 0), "nlc_conv2d: gn_in group size %d must be a multiple of the statistics granules (%d, %d)", gs, g0, g1);
-    NLC_REQUIRE((q->scale == nullptr) == (q->shift == nullptr), "nlc_conv2d: gn_in scale / shift must come together");
-    NLC_REQUIRE(!q->scale || q->ss_stride >= p.Ctot, "nlc_conv2d: gn_in ss_stride < C0+C1");
+    GnTotals t;
+    NLC_TRY(nlc_gn_totals_check("nlc_conv2d (gn_in)", p.C0, p.C1, q->groups, q->stats0, q->granule0, q->stats1, q->granule1, q->scale, q->shift,
+                                q->ss_stride, t));
     NLC_REQUIRE(q->act == NLC_ACT_NONE || q->act == NLC_ACT_SILU, "nlc_conv2d: bad gn_in act %d", q->act);
-    NLC_REQUIRE(((reinterpret_cast<uintptr_t>(q->stats0) | reinterpret_cast<uintptr_t>(q->stats1)) & 15) == 0, "nlc_conv2d: gn_in statistics must be 16-byte aligned");
-    g.tot0 = (const long long*)q->stats0; g.tot1 = (const long long*)q->stats1;
-    g.tsh0 = g0 == 4 ? 2 : 3; g.tsh1 = g1 == 4 ? 2 : 3;
+    const int gs = p.Ctot / q->groups;
+    g.tot0 = t.tot0; g.tot1 = t.tot1; g.tsh0 = t.tsh0; g.tsh1 = t.tsh1;
     g.C0 = p.C0; g.C1 = p.C1; g.gs = gs;
     g.invN = 1.0 / ((double)p.Hin * p.Win * gs);
     g.eps = q->eps; g.gamma = q->gamma; g.beta = q->beta; g.scale = q->scale; g.shift = q->shift; g.ss_stride = q->ss_stride;

@@ -192,6 +192,20 @@ __device__ __forceinline__ void gn_group_from_totals_t(const P& p, int b, int g,
     if (marks & (long long)Stat16::POISON) mean = rstd = __builtin_nanf("");
 }
 
+// Host side of the same (groupnorm.hip).  Whether a GroupNorm can be computed from totals at all is ONE rule, the exported query
+// nlc_groupnorm_totals_supported (include/nlc_hip.h); its four consumers - nlc_groupnorm_prestats / _pool2x2 / _coef and
+// nlc_conv_desc.gn_in - validate their arguments through nlc_gn_totals_check under their own name `who`: stats1 exactly when C1 > 0,
+// the rule, 16-byte alignment of the totals, the FiLM pair.  NLC_OK: t is the kernel-side view (GNParams / GnIn fields of these names).
+struct GnTotals {
+    const long long* tot0; const long long* tot1;
+    int tg0, tg1;       // channels per chunk (4 | 8)
+    int tsh0, tsh1;     // ... and their log2
+};
+int nlc_gn_totals_check(const char* who, int C0, int C1, int groups, const void* stats0, int granule0, const void* stats1, int granule1,
+                        const float* scale, const float* shift, int ss_stride, GnTotals& t);
+// the FiLM half alone (plain nlc_groupnorm): scale and shift come together, as rows of at least C floats
+int nlc_gn_film_check(const char* who, const float* scale, const float* shift, int ss_stride, int C);
+
 
 // ---- NLC_MATH_F16X3: an f32 operand as two f16 halves, x ~= hi + lo with hi = f16(x) (round to nearest), lo = f16(x - hi); the
 //      residual x - hi is exact in f32, so hi + lo carries 22 significand bits of x (lo falls into f16's subnormal range, absolute

@@ -582,6 +582,40 @@ static int affine_aligned(const float* gamma, const float* beta, const float* sc
     return ((m & 15) == 0 && (ss_stride & 3) == 0) ? 1 : 0;
 }
 
+// ---- GroupNorm from ride-along totals: the one eligibility rule and the one validator of its four consumers (conv_params.h)
+extern "C" int nlc_groupnorm_totals_supported(int C0, int C1, int groups, int granule0, int granule1) {
+    auto chunk = [](int granule) { return granule == 0 ? 8 : (granule == 4 || granule == 8) ? granule : 0; };
+    const int g0 = chunk(granule0), g1 = chunk(granule1);
+    if (!g0 || !g1 || C0 <= 0 || C1 < 0 || groups <= 0 || C0 % 8 || C1 % 8 || (C0 + C1) % groups) return 0;
+    const int gs = (C0 + C1) / groups;              // a group is a whole number of chunks of either source (it may straddle the two)
+    return gs % g0 == 0 && (C1 == 0 || gs % g1 == 0) ? 1 : 0;
+}
+
+int nlc_gn_film_check(const char* who, const float* scale, const float* shift, int ss_stride, int C) {
+    NLC_REQUIRE((scale == nullptr) == (shift == nullptr), "%s: scale/shift must come together", who);
+    NLC_REQUIRE(!scale || ss_stride >= C, "%s: ss_stride=%d < C=%d", who, ss_stride, C);
+    return NLC_OK;
+}
+
+int nlc_gn_totals_check(const char* who, int C0, int C1, int groups, const void* stats0, int granule0, const void* stats1, int granule1,
+                        const float* scale, const float* shift, int ss_stride, GnTotals& t) {
+    NLC_REQUIRE(stats0 && (C1 == 0) == (stats1 == nullptr), "%s: stats0 / stats1 must match x0 / x1 (stats1 exactly when C1 > 0)", who);
+    NLC_REQUIRE(nlc_groupnorm_totals_supported(C0, C1, groups, granule0, granule1),
+                "%s: no statistics from totals (nlc_groupnorm_totals_supported): C0=%d, C1=%d, groups=%d (group size %d), chunks of (%d, %d) channels; "
+                "chunks must be 0 (= 8), 4 or 8 and the group size a multiple of the statistics granules",
+                who, C0, C1, groups, groups > 0 ? (C0 + C1) / groups : 0, granule0, granule1);
+    NLC_REQUIRE(((reinterpret_cast<uintptr_t>(stats0) | reinterpret_cast<uintptr_t>(stats1)) & 15) == 0, "%s: statistics must be 16-byte aligned", who);
+    NLC_TRY(nlc_gn_film_check(who, scale, shift, ss_stride, C0 + C1));
+    t.tot0 = (const long long*)stats0; t.tot1 = (const long long*)stats1;
+    t.tg0 = granule0 == 4 ? 4 : 8; t.tg1 = granule1 == 4 ? 4 : 8;
+    t.tsh0 = t.tg0 == 4 ? 2 : 3; t.tsh1 = t.tg1 == 4 ? 2 : 3;
+    return NLC_OK;
+}
+
+static void use_totals(GNParams& p, const GnTotals& t) {
+    p.tot0 = t.tot0; p.tot1 = t.tot1; p.tg0 = t.tg0; p.tg1 = t.tg1; p.tsh0 = t.tsh0; p.tsh1 = t.tsh1;
+}
+
 // Pixels per apply workgroup: `unit` (= ps x unroll x 4 trips) for the big maps, capped so the grid stays <= GN_APPLY_MAXBLK
 // workgroups; halved down to `ps` (one chunk per thread) while the launch would have fewer than 512 workgroups - the 8x8 ... 32x32
 // levels otherwise ran 16 ... 128 workgroups of four dependent trips each on a 256-CU chip (12-15 us per launch instead of ~5).
@@ -610,8 +644,7 @@ extern "C" int nlc_groupnorm(const void* x0, const void* x1, int C0, int C1, int
     const int C = C0 + C1;
     NLC_REQUIRE(C % groups == 0, "nlc_groupnorm: C=%d not divisible by groups=%d", C, groups);
     NLC_REQUIRE(C / per <= NT * MAX_SLOTS, "nlc_groupnorm: C=%d too large", C);
-    NLC_REQUIRE((scale == nullptr) == (shift == nullptr), "nlc_groupnorm: scale/shift must come together");
-    NLC_REQUIRE(!scale || ss_stride >= C, "nlc_groupnorm: ss_stride < C");
+    NLC_TRY(nlc_gn_film_check("nlc_groupnorm", scale, shift, ss_stride, C));
     GNParams p;
     fill_params(p, x0, x1, C0, C1, B, HW, groups, dtype);
     p.eps = eps; p.gamma = gamma; p.beta = beta; p.scale = scale; p.shift = shift; p.ss_stride = ss_stride;
@@ -620,12 +653,10 @@ extern "C" int nlc_groupnorm(const void* x0, const void* x1, int C0, int C1, int
     const size_t lds_apply = ((size_t)2 * p.C + 2 * p.G) * sizeof(float);
     NLC_REQUIRE(lds_stats <= 64 * 1024 && lds_apply <= 64 * 1024, "nlc_groupnorm: LDS budget exceeded (C=%d)", C);
     hipStream_t st = (hipStream_t)stream;
-    const int es = nlc_is16(dtype) ? 2 : 4;
     int64_t chunks = (int64_t)HW * p.nch;
     int nblk2 = cdiv(chunks, NT * 8);
     if (nblk2 < 1) nblk2 = 1;
     if (nblk2 > 2048 / B + 1) nblk2 = 2048 / B + 1;
-    (void)es;
     static const bool fast_ok = !(getenv("NLC_GN_FAST") && getenv("NLC_GN_FAST")[0] == '0');   // diagnostic switch
     if (p.nslot == 1 && fast_ok) {
         float* stat = reinterpret_cast<float*>(p.ws + (int64_t)B * MAX_NBLK * groups * 3);
@@ -651,25 +682,18 @@ extern "C" int nlc_groupnorm_prestats(const void* x0, const void* x1, int C0, in
                                       const float* gamma, const float* beta, const float* scale, const float* shift,
                                       int ss_stride, int silu, void* out, int dtype,
                                       const void* stats0, int gran0, const void* stats1, int gran1, void* stream) {
-    const int g0 = gran0 == 4 ? 4 : 8, g1 = gran1 == 4 ? 4 : 8;
-    NLC_REQUIRE((gran0 == 0 || gran0 == 4 || gran0 == 8) && (gran1 == 0 || gran1 == 4 || gran1 == 8), "nlc_groupnorm_prestats: granules must be 0 (= 8), 4 or 8");
     NLC_REQUIRE(nlc_is16(dtype), "nlc_groupnorm_prestats: bf16 / f16 only (the f32 path computes its statistics itself)");
     NLC_REQUIRE(x0 && out && stats0, "nlc_groupnorm_prestats: null pointer");
     NLC_REQUIRE(B > 0 && HW > 0 && C0 > 0 && C1 >= 0 && groups > 0, "nlc_groupnorm_prestats: bad dims");
-    NLC_REQUIRE((C1 == 0) == (x1 == nullptr) && (C1 == 0) == (stats1 == nullptr), "nlc_groupnorm_prestats: x1 / stats1 / C1 mismatch");
-    const int C = C0 + C1;
-    NLC_REQUIRE(C % groups == 0 && (C / groups) % g0 == 0 && (C1 == 0 || (C / groups) % g1 == 0) && C0 % 8 == 0 && C1 % 8 == 0,
-                "nlc_groupnorm_prestats: group size %d must be a multiple of the statistics granules (%d, %d) and C0=%d, C1=%d of 8", C / groups, g0, g1, C0, C1);
-    NLC_REQUIRE(C / 8 <= NT, "nlc_groupnorm_prestats: C=%d too large for the one-chunk-per-thread apply kernel", C);
-    NLC_REQUIRE((scale == nullptr) == (shift == nullptr), "nlc_groupnorm_prestats: scale/shift must come together");
-    NLC_REQUIRE(!scale || ss_stride >= C, "nlc_groupnorm_prestats: ss_stride < C");
-    NLC_REQUIRE(((reinterpret_cast<uintptr_t>(stats0) | reinterpret_cast<uintptr_t>(stats1)) & 15) == 0, "nlc_groupnorm_prestats: statistics must be 16-byte aligned");
+    NLC_REQUIRE((C1 == 0) == (x1 == nullptr), "nlc_groupnorm_prestats: x1 / C1 mismatch");
+    GnTotals t;
+    NLC_TRY(nlc_gn_totals_check("nlc_groupnorm_prestats", C0, C1, groups, stats0, gran0, stats1, gran1, scale, shift, ss_stride, t));
+    NLC_REQUIRE((C0 + C1) / 8 <= NT, "nlc_groupnorm_prestats: C=%d too large for the one-chunk-per-thread apply kernel", C0 + C1);
     GNParams p;
     fill_params(p, x0, x1, C0, C1, B, HW, groups, dtype);
     p.eps = eps; p.gamma = gamma; p.beta = beta; p.scale = scale; p.shift = shift; p.ss_stride = ss_stride;
     p.silu = silu; p.out = (char*)out; p.ws = nullptr;
-    p.tot0 = (const long long*)stats0; p.tot1 = (const long long*)stats1; p.tg0 = g0; p.tg1 = g1;
-    p.tsh0 = g0 == 4 ? 2 : 3; p.tsh1 = g1 == 4 ? 2 : 3;
+    use_totals(p, t);
     p.vec_affine = affine_aligned(gamma, beta, scale, shift, ss_stride);
     const int ppb = apply_pix_per_block(HW, B, p.ps, p.ps * UNR * 4);
     // ONE launch: every apply thread derives its channels' (a, b) from the totals (gn_group_from_totals)
@@ -682,18 +706,16 @@ extern "C" int nlc_groupnorm_pool2x2(const void* x, int C, int B, int H, int W, 
                                      const float* beta, const float* scale, const float* shift, int ss_stride, int silu,
                                      void* out_norm, void* out_x, void* workspace, int dtype, const void* stats0, int gran0,
                                      void* stream) {
-    const int g0 = gran0 == 4 ? 4 : 8;
-    NLC_REQUIRE(gran0 == 0 || gran0 == 4 || gran0 == 8, "nlc_groupnorm_pool2x2: granule must be 0 (= 8), 4 or 8");
     NLC_REQUIRE(nlc_dtype_ok(dtype), "nlc_groupnorm_pool2x2: bad dtype %d", dtype);
     const int per = nlc_is16(dtype) ? 8 : 4;
     NLC_REQUIRE(x && out_norm && out_x && (workspace || stats0), "nlc_groupnorm_pool2x2: null pointer");
     NLC_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && groups > 0 && H % 2 == 0 && W % 2 == 0, "nlc_groupnorm_pool2x2: bad dims (H, W even)");
     NLC_REQUIRE(C % per == 0 && C % groups == 0, "nlc_groupnorm_pool2x2: C=%d must be a multiple of %d and of groups=%d", C, per, groups);
     NLC_REQUIRE(C / per <= NT, "nlc_groupnorm_pool2x2: C=%d too large for the one-chunk-per-thread kernels", C);
-    NLC_REQUIRE((scale == nullptr) == (shift == nullptr), "nlc_groupnorm_pool2x2: scale/shift must come together");
-    NLC_REQUIRE(!scale || ss_stride >= C, "nlc_groupnorm_pool2x2: ss_stride < C");
-    NLC_REQUIRE(!stats0 || (nlc_is16(dtype) && (C / groups) % g0 == 0 && (reinterpret_cast<uintptr_t>(stats0) & 15) == 0),
-                "nlc_groupnorm_pool2x2: ride-along statistics are bf16 / f16 only, group size a multiple of their granule");
+    NLC_REQUIRE(!stats0 || nlc_is16(dtype), "nlc_groupnorm_pool2x2: ride-along statistics are bf16 / f16 only");
+    GnTotals t;
+    if (stats0) NLC_TRY(nlc_gn_totals_check("nlc_groupnorm_pool2x2", C, 0, groups, stats0, gran0, nullptr, 0, scale, shift, ss_stride, t));
+    else NLC_TRY(nlc_gn_film_check("nlc_groupnorm_pool2x2", scale, shift, ss_stride, C));
     const int HW = H * W;
     GNParams p;
     fill_params(p, x, nullptr, C, 0, B, HW, groups, dtype);
@@ -702,7 +724,7 @@ extern "C" int nlc_groupnorm_pool2x2(const void* x, int C, int B, int H, int W, 
     hipStream_t st = (hipStream_t)stream;
     float* stat = nullptr;
     if (stats0) {
-        p.tot0 = (const long long*)stats0; p.tg0 = g0; p.tsh0 = g0 == 4 ? 2 : 3;   // the apply threads derive (a, b) from the totals: no other launch
+        use_totals(p, t);                            // the apply threads derive (a, b) from the totals: no other launch
         p.vec_affine = affine_aligned(gamma, beta, scale, shift, ss_stride);
     } else {
         stat = reinterpret_cast<float*>(p.ws + (int64_t)B * MAX_NBLK * groups * 3);
@@ -722,21 +744,15 @@ extern "C" int nlc_groupnorm_pool2x2(const void* x, int C, int B, int H, int W, 
 extern "C" int nlc_groupnorm_coef(int C0, int C1, int B, int HW, int groups, float eps, const float* gamma, const float* beta,
                                   const float* scale, const float* shift, int ss_stride, const void* stats0, int gran0,
                                   const void* stats1, int gran1, float* coef, void* stream) {
-    const int g0 = gran0 == 4 ? 4 : 8, g1 = gran1 == 4 ? 4 : 8;
     NLC_REQUIRE(coef && stats0, "nlc_groupnorm_coef: null pointer");
     NLC_REQUIRE(B > 0 && HW > 0 && C0 > 0 && C1 >= 0 && groups > 0, "nlc_groupnorm_coef: bad dims");
-    NLC_REQUIRE((C1 == 0) == (stats1 == nullptr), "nlc_groupnorm_coef: stats1 / C1 mismatch");
+    GnTotals t;
+    NLC_TRY(nlc_gn_totals_check("nlc_groupnorm_coef", C0, C1, groups, stats0, gran0, stats1, gran1, scale, shift, ss_stride, t));
     const int C = C0 + C1;
-    NLC_REQUIRE(C % groups == 0 && (C / groups) % g0 == 0 && (C1 == 0 || (C / groups) % g1 == 0) && C0 % 8 == 0 && C1 % 8 == 0,
-                "nlc_groupnorm_coef: group size %d must be a multiple of the statistics granules and C0=%d, C1=%d of 8", C / groups, C0, C1);
-    NLC_REQUIRE((scale == nullptr) == (shift == nullptr), "nlc_groupnorm_coef: scale/shift must come together");
-    NLC_REQUIRE(!scale || ss_stride >= C, "nlc_groupnorm_coef: ss_stride < C");
-    NLC_REQUIRE(((reinterpret_cast<uintptr_t>(stats0) | reinterpret_cast<uintptr_t>(stats1)) & 15) == 0, "nlc_groupnorm_coef: statistics must be 16-byte aligned");
     GNParams p{};
     p.C0 = C0; p.C1 = C1; p.C = C; p.B = B; p.HW = HW; p.G = groups; p.gs = C / groups; p.eps = eps;
     p.gamma = gamma; p.beta = beta; p.scale = scale; p.shift = shift; p.ss_stride = ss_stride;
-    p.tot0 = (const long long*)stats0; p.tot1 = (const long long*)stats1; p.tg0 = g0; p.tg1 = g1;
-    p.tsh0 = g0 == 4 ? 2 : 3; p.tsh1 = g1 == 4 ? 2 : 3;
+    use_totals(p, t);
     p.invN = 1.0 / ((double)HW * p.gs); p.div_gs = FastDiv::make(p.gs);
     hipLaunchKernelGGL(gn_coef_from_totals_kernel, dim3(cdiv(C, NT), B), dim3(NT), 0, (hipStream_t)stream, p, coef);
     NLC_CHECK_LAUNCH("nlc_groupnorm_coef");

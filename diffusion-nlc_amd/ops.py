@@ -164,10 +164,6 @@ def stats_granule(cout: int, groups_hint: int = 32) -> int:
     return 4 if (STATS_GRANULE_4 and cout % 8 == 0 and gs and gs % 8 != 0 and gs % 4 == 0) else 8
 
 
-def _stats_gran_of(t: torch.Tensor, st: torch.Tensor) -> int:
-    return t.shape[-1] // st.shape[1]
-
-
 # ---- ride-along GroupNorm statistics: zeroed accumulators ---------------------------------------------------------------------
 # A convolution ADDS the (sum, sum of squares) totals of its output to an int64 [B, C/g, 4] buffer that must be zero when it starts
 # (include/nlc_hip.h, nlc_conv_desc.stats_out).  Inside a network evaluation the buffers of all its convolutions are slices of ONE
@@ -254,6 +250,42 @@ def ride_stats(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
     if tag is not None and tag[0].gen != tag[1]:
         return None
     return st
+
+
+def _ride_totals(x0: torch.Tensor, x1: Optional[torch.Tensor], groups: int) -> Optional[tuple]:
+    """``(stats0, granule0, stats1, granule1)`` when a GroupNorm with ``groups`` groups over cat(x0, x1) can take its statistics from the
+    totals that rode along with the producers of x0 / x1, else None (f32 models, a source without attached totals, group sizes that the
+    totals' chunks cannot express): the consumer then computes the statistics itself.  The rule is the library's
+    (nlc_groupnorm_totals_supported); a missing x1 has granule 0."""
+    if not FUSED_GN_STATS or not is16(x0.dtype):
+        return None
+    s0, s1 = ride_stats(x0), ride_stats(x1)
+    if s0 is None or (x1 is not None and s1 is None):
+        return None
+    C0, C1 = x0.shape[-1], 0 if x1 is None else x1.shape[-1]
+    g0, g1 = C0 // s0.shape[1], 0 if s1 is None else C1 // s1.shape[1]
+    if not _ext.load().nlc_groupnorm_totals_supported(C0, C1, groups, g0, g1):
+        return None
+    return s0, g0, s1, g1
+
+
+def _film_stride(scale: Optional[torch.Tensor], shift: Optional[torch.Tensor], C: int, who: str) -> int:
+    """The row stride (nlc ``ss_stride``) of a FiLM pair, 0 without one.  scale / shift are usually the two halves of one [B, 2C] embedding
+    row: CUDA f32 [B, >= C] views with unit inner stride that share a row stride, both or neither."""
+    if scale is None and shift is None:
+        return 0
+    if scale is None or shift is None:
+        raise ValueError(f"{who}: scale and shift come together")
+    for nm, v in (("scale", scale), ("shift", shift)):
+        if v.dtype != torch.float32:
+            raise ValueError(f"{who}: {nm} must be float32, got {v.dtype}")
+        if v.dim() != 2 or v.stride(1) != 1 or v.shape[1] < C:
+            raise ValueError(f"{who}: {nm} must be a [B, >={C}] view with unit inner stride, got shape {tuple(v.shape)}")
+    if shift.stride(0) != scale.stride(0):
+        raise ValueError(f"{who}: scale/shift must share a row stride")
+    if not (scale.is_cuda and shift.is_cuda):
+        raise ValueError(f"{who}: scale/shift must live on the GPU")
+    return scale.stride(0)
 
 
 def conv2d(x0: torch.Tensor, pw: PackedConv, *, x1: Optional[torch.Tensor] = None, stride: int = 1,
@@ -411,26 +443,11 @@ def gn_in_spec(x0: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[t
     """(nlc_gn_in, keep-alive...) for conv2d(gn_in=...): GroupNorm (+FiLM) (+SiLU) over cat(x0, x1) described by the totals that rode
     along with the producing convolutions, or None when they are not available (f32 models, inputs without attached statistics,
     group sizes that the totals' chunks cannot express): the caller then runs groupnorm()."""
-    if not FUSED_GN_STATS or not is16(x0.dtype):
+    tot = _ride_totals(x0, x1, groups)
+    if tot is None:
         return None
-    C0 = x0.shape[-1]
-    C1 = 0 if x1 is None else x1.shape[-1]
-    Ctot = C0 + C1
-    if C0 % 8 or C1 % 8 or Ctot % groups:
-        return None
-    s0, s1 = ride_stats(x0), ride_stats(x1)
-    if s0 is None or (x1 is not None and s1 is None):
-        return None
-    g0 = _stats_gran_of(x0, s0)
-    g1 = _stats_gran_of(x1, s1) if s1 is not None else 8
-    gs = Ctot // groups
-    if gs % g0 or (x1 is not None and gs % g1):
-        return None
-    ss_stride = 0
-    if scale is not None:
-        ss_stride = scale.stride(0)
-        if shift is None or shift.stride(0) != ss_stride or scale.stride(1) != 1 or shift.stride(1) != 1 or scale.dtype != torch.float32:
-            raise ValueError("gn_in_spec: scale/shift must be row-strided f32 views sharing a row stride")
+    s0, g0, s1, g1 = tot
+    ss_stride = _film_stride(scale, shift, x0.shape[-1] + (0 if x1 is None else x1.shape[-1]), "gn_in_spec")
     spec = _ext.GnIn(stats0=s0.data_ptr(), stats1=_ptr(s1), granule0=g0, granule1=g1, groups=groups, eps=eps, gamma=_ptr(gamma),
                      beta=_ptr(beta), scale=_ptr(scale), shift=_ptr(shift), ss_stride=ss_stride, act=ACT_SILU if silu else ACT_NONE)
     return (spec, s0, s1, gamma, beta, scale, shift)
@@ -511,29 +528,21 @@ def _grown(nbytes: int) -> int:
     return n
 
 
-def _conv_workspace(device, nbytes: int) -> torch.Tensor:
-    """Per (device, stream) scratch for nlc_conv2d's split-K partials; grows geometrically to cover the largest request.  Allocated
-    ZEROED: its first 4 KiB are the library's arrival counters, which every launch leaves zero (include/nlc_hip.h,
-    nlc_conv_desc.workspace)."""
+def _workspace(cache: dict, device, nbytes: int, zeroed: bool) -> torch.Tensor:
+    """Per (device, stream) scratch out of ``cache`` (_conv_ws | _gn_ws); grows geometrically to cover the largest request."""
     key = (device.index if device.index is not None else torch.cuda.current_device(), torch.cuda.current_stream().cuda_stream)
-    ws = _conv_ws.get(key)
+    ws = cache.get(key)
     if ws is None or ws.numel() * 4 < nbytes:
         if ws is not None:
             _ws_retired.append(ws)          # a captured hipGraph may still reference the smaller buffer: never hand it back
-        ws = torch.zeros(_grown(nbytes) // 4, device=device, dtype=torch.float32)
-        _conv_ws[key] = ws
+        ws = cache[key] = (torch.zeros if zeroed else torch.empty)(_grown(nbytes) // 4, device=device, dtype=torch.float32)
     return ws
 
 
-def _gn_workspace(device, nbytes: int) -> torch.Tensor:
-    key = (device.index if device.index is not None else torch.cuda.current_device(), torch.cuda.current_stream().cuda_stream)
-    ws = _gn_ws.get(key)
-    if ws is None or ws.numel() * 4 < nbytes:
-        if ws is not None:
-            _ws_retired.append(ws)
-        ws = torch.empty(_grown(nbytes) // 4, device=device, dtype=torch.float32)
-        _gn_ws[key] = ws
-    return ws
+def _conv_workspace(device, nbytes: int) -> torch.Tensor:
+    """nlc_conv2d's split-K partials.  Allocated ZEROED: its first 4 KiB are the library's arrival counters, which every launch leaves
+    zero (include/nlc_hip.h, nlc_conv_desc.workspace)."""
+    return _workspace(_conv_ws, device, nbytes, zeroed=True)
 
 
 def groupnorm(x0: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor], *, groups: int,
@@ -551,29 +560,16 @@ def groupnorm(x0: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[to
         C1 = x1.shape[-1]
     Ctot = C0 + C1
     out = torch.empty(*x0.shape[:-1], Ctot, device=x0.device, dtype=dt)
-    ss_stride = 0
-    if scale is not None:
-        # scale / shift are usually the two halves of one [B, 2C] embedding row: row-strided views
-        for nm, v in (("scale", scale), ("shift", shift)):
-            if v is None or v.dtype != torch.float32 or not v.is_cuda or v.dim() != 2 or v.stride(1) != 1 \
-                    or v.shape[1] < Ctot:
-                raise ValueError(f"groupnorm: {nm} must be a CUDA f32 [B, >=C] view with unit inner stride")
-        ss_stride = scale.stride(0)
-        if shift.stride(0) != ss_stride:
-            raise ValueError("groupnorm: scale/shift must share a row stride")
-    if FUSED_GN_STATS and is16(dt) and Ctot % groups == 0 and C0 % 8 == 0 and C1 % 8 == 0 and Ctot // 8 <= 256:
-        s0 = ride_stats(x0)
-        s1 = ride_stats(x1)
-        gs = Ctot // groups
-        g0 = _stats_gran_of(x0, s0) if s0 is not None else 8
-        g1 = _stats_gran_of(x1, s1) if s1 is not None else 8
-        if s0 is not None and (x1 is None or s1 is not None) and gs % g0 == 0 and (x1 is None or gs % g1 == 0):
-            # the totals came with the producing convolutions: ONE streaming launch (its threads derive their coefficients)
-            check(lib.nlc_groupnorm_prestats(x0.data_ptr(), _ptr(x1), C0, C1, B, HW, groups, eps, _ptr(gamma), _ptr(beta),
-                                             _ptr(scale), _ptr(shift), ss_stride, 1 if silu else 0, out.data_ptr(),
-                                             dtype_enum(dt), s0.data_ptr(), g0, _ptr(s1), g1, _stream()), "nlc_groupnorm_prestats")
-            return out
-    ws = _gn_workspace(x0.device, lib.nlc_groupnorm_workspace_bytes(B, HW, Ctot, groups))
+    ss_stride = _film_stride(scale, shift, Ctot, "groupnorm")
+    tot = _ride_totals(x0, x1, groups) if Ctot // 8 <= 256 else None       # (the one-launch apply kernel: one 16-byte chunk per thread)
+    if tot is not None:
+        # the totals came with the producing convolutions: ONE streaming launch (its threads derive their coefficients)
+        s0, g0, s1, g1 = tot
+        check(lib.nlc_groupnorm_prestats(x0.data_ptr(), _ptr(x1), C0, C1, B, HW, groups, eps, _ptr(gamma), _ptr(beta),
+                                         _ptr(scale), _ptr(shift), ss_stride, 1 if silu else 0, out.data_ptr(),
+                                         dtype_enum(dt), s0.data_ptr(), g0, _ptr(s1), g1, _stream()), "nlc_groupnorm_prestats")
+        return out
+    ws = _workspace(_gn_ws, x0.device, lib.nlc_groupnorm_workspace_bytes(B, HW, Ctot, groups), zeroed=False)
     check(lib.nlc_groupnorm(x0.data_ptr(), _ptr(x1), C0, C1, B, HW, groups, eps, _ptr(gamma), _ptr(beta),
                             _ptr(scale), _ptr(shift), ss_stride, 1 if silu else 0, out.data_ptr(), ws.data_ptr(),
                             dtype_enum(dt), _stream()), "nlc_groupnorm")
@@ -592,22 +588,9 @@ def groupnorm_pool2x2(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Opti
     B, H, W, Cc = x.shape
     out_h = torch.empty(B, H // 2, W // 2, Cc, device=x.device, dtype=dt)
     out_x = torch.empty_like(out_h)
-    ss_stride = 0
-    if scale is not None:
-        for nm, v in (("scale", scale), ("shift", shift)):
-            if v is None or v.dtype != torch.float32 or not v.is_cuda or v.dim() != 2 or v.stride(1) != 1 or v.shape[1] < Cc:
-                raise ValueError(f"groupnorm_pool2x2: {nm} must be a CUDA f32 [B, >=C] view with unit inner stride")
-        ss_stride = scale.stride(0)
-        if shift.stride(0) != ss_stride:
-            raise ValueError("groupnorm_pool2x2: scale/shift must share a row stride")
-    ws = _gn_workspace(x.device, lib.nlc_groupnorm_workspace_bytes(B, H * W, Cc, groups))
-    s0, g0 = None, 8
-    if FUSED_GN_STATS and is16(dt) and Cc % groups == 0:
-        s0 = ride_stats(x)
-        if s0 is not None:
-            g0 = _stats_gran_of(x, s0)
-            if (Cc // groups) % g0:
-                s0 = None
+    ss_stride = _film_stride(scale, shift, Cc, "groupnorm_pool2x2")
+    ws = _workspace(_gn_ws, x.device, lib.nlc_groupnorm_workspace_bytes(B, H * W, Cc, groups), zeroed=False)
+    s0, g0 = (_ride_totals(x, None, groups) or (None, 0))[:2]         # no totals: the library computes the statistics by a pass over x
     check(lib.nlc_groupnorm_pool2x2(x.data_ptr(), Cc, B, H, W, groups, eps, _ptr(gamma), _ptr(beta), _ptr(scale), _ptr(shift),
                                     ss_stride, 1 if silu else 0, out_h.data_ptr(), out_x.data_ptr(), ws.data_ptr(), dtype_enum(dt),
                                     _ptr(s0), g0, _stream()), "nlc_groupnorm_pool2x2")
@@ -641,27 +624,15 @@ def groupnorm_coef(x0: torch.Tensor, gamma, beta, *, groups: int, eps: float, x1
     with the producing convolutions - for conv2d(gn_coef=...).  None when they are not available (f32 models, inputs without
     attached statistics, group sizes that 8-channel chunks cannot express): the caller then runs groupnorm()."""
     lib = _ext.load()
-    if not FUSED_GN_STATS or not is16(x0.dtype):             # (totals ride along with 16-bit tensors only)
+    tot = _ride_totals(x0, x1, groups)
+    if tot is None:
         return None
+    s0, g0, s1, g1 = tot
     B, C0 = x0.shape[0], x0.shape[-1]
     C1 = 0 if x1 is None else x1.shape[-1]
     Ctot = C0 + C1
-    if C0 % 8 or C1 % 8 or Ctot % groups:
-        return None
-    s0 = ride_stats(x0)
-    s1 = ride_stats(x1)
-    if s0 is None or (x1 is not None and s1 is None):
-        return None
-    g0 = _stats_gran_of(x0, s0)
-    g1 = _stats_gran_of(x1, s1) if s1 is not None else 8
-    if (Ctot // groups) % g0 or (x1 is not None and (Ctot // groups) % g1):
-        return None
     HW = x0.numel() // (B * C0)
-    ss_stride = 0
-    if scale is not None:
-        ss_stride = scale.stride(0)
-        if shift is None or shift.stride(0) != ss_stride or scale.stride(1) != 1 or shift.stride(1) != 1:
-            raise ValueError("groupnorm_coef: scale/shift must be row-strided f32 views sharing a row stride")
+    ss_stride = _film_stride(scale, shift, Ctot, "groupnorm_coef")
     coef = torch.empty(B * Ctot * 2 + 128, device=x0.device, dtype=torch.float32)        # + 512 bytes: the consumer's DMA reads whole 1-KiB pieces
     check(lib.nlc_groupnorm_coef(C0, C1, B, HW, groups, eps, _ptr(gamma), _ptr(beta), _ptr(scale), _ptr(shift), ss_stride,
                                  s0.data_ptr(), g0, _ptr(s1), g1, coef.data_ptr(), _stream()), "nlc_groupnorm_coef")

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define NLC_ABI_VERSION 8
+#define NLC_ABI_VERSION 9
 
 enum { NLC_F32 = 0, NLC_BF16 = 1, NLC_F16 = 2 };
 /* matrix arithmetic of nlc_conv2d on NLC_F32 tensors (nlc_conv_desc.math; weights must be packed for the same mode):
@@ -128,7 +128,7 @@ int nlc_pack_conv_weights_ex(const float* w, const float* bias, int Cout, int Ci
  * src/edm_networks.py:185-192) costs neither a launch nor a pass over HBM.  Same arithmetic as nlc_groupnorm_prestats:
  *   y = act( ((x - mean) * rstd * gamma + beta) * (1 + scale[b][c]) + shift[b][c] ),   zero padding stays zero.
  * Fields as in nlc_groupnorm_prestats: stats0 / stats1 = int64 [B][C0/g0 | C1/g1][4] totals of x0 / x1 (stats1 NULL iff C1 == 0),
- * granule 0 | 8 | 4; (C0+C1)/groups a multiple of both granules; gamma / beta f32 [C0+C1] or NULL; scale / shift f32 row-strided
+ * granule 0 | 8 | 4, eligible per nlc_groupnorm_totals_supported; gamma / beta f32 [C0+C1] or NULL; scale / shift f32 row-strided
  * [B][>= C0+C1] views (both or neither); act = NLC_ACT_NONE | NLC_ACT_SILU. */
 typedef struct nlc_gn_in {
     const void* stats0; const void* stats1;
@@ -281,25 +281,29 @@ int nlc_groupnorm(const void* x0, const void* x1, int C0, int C1, int B, int HW,
                   int groups, float eps, const float* gamma, const float* beta,
                   const float* scale, const float* shift, int ss_stride,
                   int silu, void* out, void* workspace, int dtype, void* stream);
-/* Same, but the statistics come from the producing convolutions' epilogues (nlc_conv_desc.stats_out) instead of a pass
- * over the input: stats0 / stats1 = the int64 [B][C0/g0 | C1/g1][4] totals of x0 / x1.  ONE launch: every thread of the
- * streaming kernel derives its channels' coefficients from the totals of the one or two groups they lie in (f64:
- * var = E[x^2] - E[x]^2).  Requires a 16-bit dtype, (C0+C1)/groups a multiple of both granules and C0, C1 multiples of 8 (a
- * group may straddle the two sources).  No workspace. */
+/* (ABI v9) 1 if a GroupNorm with `groups` groups over cat(x0 [C0 channels], x1 [C1 channels, 0 = none]) can take its statistics from
+ * ride-along totals of granule0 / granule1 channels per chunk (0 = 8), else 0.  Host only: launches nothing, reads no pointer.
+ * The one rule of the four consumers of the totals - nlc_groupnorm_prestats, nlc_groupnorm_pool2x2 (with stats0), nlc_groupnorm_coef
+ * and nlc_conv_desc.gn_in - which reject (NLC_EINVAL) what it answers 0 for; a group may straddle the two sources. */
+int nlc_groupnorm_totals_supported(int C0, int C1, int groups, int granule0, int granule1);
+/* Same as nlc_groupnorm, but the statistics come from the producing convolutions' epilogues (nlc_conv_desc.stats_out) instead of a
+ * pass over the input: stats0 / stats1 = the int64 [B][C0/g0 | C1/g1][4] totals of x0 / x1 (stats1 NULL iff C1 == 0, 16-byte
+ * aligned).  ONE launch: every thread of the streaming kernel derives its channels' coefficients from the totals of the one or two
+ * groups they lie in (f64: var = E[x^2] - E[x]^2).  Requires a 16-bit dtype, nlc_groupnorm_totals_supported and C0+C1 <= 2048 (one
+ * 16-byte chunk per thread).  No workspace. */
 int nlc_groupnorm_prestats(const void* x0, const void* x1, int C0, int C1, int B, int HW,
                            int groups, float eps, const float* gamma, const float* beta,
                            const float* scale, const float* shift, int ss_stride,
                            int silu, void* out, int dtype,
                            const void* stats0, int granule0, const void* stats1, int granule1, void* stream);
-/* granule0 / granule1: channels per chunk of stats0 / stats1 (0 or 8, or 4 - nlc_conv_desc.stats_granule of the producer); the
- * group size must be a multiple of both. */
+/* granule0 / granule1: channels per chunk of stats0 / stats1 (0 or 8, or 4 - nlc_conv_desc.stats_granule of the producer). */
 
 /* The two branches of a down-sampling ResBlock from ONE read of x (src/unet_adm.py:193-195: h = in_rest(x); h = h_upd(h);
  * x = x_upd(x), both AvgPool2d(2)):  out_norm = avgpool2x2(act(GroupNorm(x) (FiLM))),  out_x = avgpool2x2(x), both
  * [B][H/2][W/2][C]; the full-resolution normalised tensor is never written.  Statistics: stats0 as in
- * nlc_groupnorm_prestats (16-bit), or NULL -> computed here by a pass over x.  f32: bit-identical to nlc_groupnorm followed by
- * nlc_avgpool2x2; 16-bit: the pooled mean is taken of the f32 activations (one rounding less).  Same workspace as nlc_groupnorm
- * (may be NULL when stats0 is given). */
+ * nlc_groupnorm_prestats (16-bit, nlc_groupnorm_totals_supported(C, 0, groups, granule0, 0)), or NULL -> computed here by a pass
+ * over x.  f32: bit-identical to nlc_groupnorm followed by nlc_avgpool2x2; 16-bit: the pooled mean is taken of the f32 activations
+ * (one rounding less).  Same workspace as nlc_groupnorm (may be NULL when stats0 is given). */
 int nlc_groupnorm_pool2x2(const void* x, int C, int B, int H, int W, int groups, float eps, const float* gamma,
                           const float* beta, const float* scale, const float* shift, int ss_stride, int silu,
                           void* out_norm, void* out_x, void* workspace, int dtype, const void* stats0, int granule0,
@@ -307,7 +311,8 @@ int nlc_groupnorm_pool2x2(const void* x, int C, int B, int H, int W, int groups,
 
 /* The per-(image, channel) coefficients of the same normalisation, for the convolution that applies it in its LDS prologue
  * (nlc_conv_desc.gn_coef): coef[b][c] = (a, b) with  a = rstd*gamma*(1+scale),  b = (beta - mean*rstd*gamma)*(1+scale) + shift,
- * statistics from the producing convolutions' epilogues exactly as in nlc_groupnorm_prestats (same f64 arithmetic on the totals).
+ * statistics from the producing convolutions' epilogues exactly as in nlc_groupnorm_prestats (same f64 arithmetic on the totals; needs
+ * nlc_groupnorm_totals_supported).
  * coef: float [B][C0+C1][2] (+ >= 512 bytes of slack behind it for the consumer's DMA). */
 int nlc_groupnorm_coef(int C0, int C1, int B, int HW, int groups, float eps, const float* gamma, const float* beta,
                        const float* scale, const float* shift, int ss_stride, const void* stats0, int granule0,

@@ -178,6 +178,144 @@ def test_conv_queries_are_views_of_one_plan():
         assert seen[q] == {False, True}, q
 
 
+def _totals_rule(C0, C1, groups, g0, g1):
+    """nlc_groupnorm_totals_supported restated: granules 0 (= 8), 4 or 8; C0, C1 multiples of 8; groups divides C0 + C1; the group size a
+    multiple of each source's granule."""
+    if g0 not in (0, 4, 8) or g1 not in (0, 4, 8) or C0 % 8 or C1 % 8 or (C0 + C1) % groups:
+        return 0
+    gs = (C0 + C1) // groups
+    return int(gs % (g0 or 8) == 0 and (C1 == 0 or gs % (g1 or 8) == 0))
+
+
+def test_groupnorm_totals_supported_is_the_rule():
+    from diffusion_nlc_amd import _ext
+    lib = _ext.load()
+    n = 0
+    for C0 in (8, 24, 64, 96, 128, 132):
+        for C1 in (0, 8, 64, 100):
+            for groups in (1, 3, 8, 32):
+                for g0 in (0, 4, 8, 5):
+                    for g1 in (0, 4, 8, 5):
+                        assert lib.nlc_groupnorm_totals_supported(C0, C1, groups, g0, g1) == _totals_rule(C0, C1, groups, g0, g1), (C0, C1, groups, g0, g1)
+                        n += 1
+    assert n == 1536
+    # what the networks produce: 128 channels / 32 groups at granule 4, 256 / 32 at granule 8, a 64 + 64 concatenation at mixed granules
+    # (16-channel groups: at 32 groups its 4-channel groups are no multiple of the second source's granule 8)
+    for args in ((128, 0, 32, 4, 0), (256, 0, 32, 8, 0), (256, 0, 32, 0, 0), (64, 64, 8, 4, 8), (64, 64, 8, 8, 4), (128, 128, 32, 4, 4), (128, 256, 8, 4, 8)):
+        assert lib.nlc_groupnorm_totals_supported(*args) == 1, args
+    for args in ((64, 64, 32, 4, 8), (128, 256, 32, 4, 8), (96, 0, 32, 4, 0)):      # 4-, 12- and 3-channel groups against 8- / 4-channel chunks
+        assert lib.nlc_groupnorm_totals_supported(*args) == 0, args
+    assert lib.nlc_groupnorm_totals_supported(0, 0, 32, 8, 8) == 0 and lib.nlc_groupnorm_totals_supported(64, 0, 0, 8, 8) == 0
+
+
+def _cpu_with_totals(C, gran, dtype=torch.bfloat16):
+    """A CPU activation [2, 4, 4, C] with hand-attached (zero) ride-along totals of `gran` channels per chunk."""
+    t = torch.zeros(2, 4, 4, C, dtype=dtype)
+    t._nlc_stats = torch.zeros(2, C // gran, 4, dtype=torch.int64)
+    return t
+
+
+def test_ride_totals_decides_on_the_host(monkeypatch):
+    """ops._ride_totals needs no GPU to decide, and decides what the library's query answers."""
+    from diffusion_nlc_amd import _ext, ops
+    lib = _ext.load()
+    seen = set()
+    for C0, g0 in ((128, 4), (128, 8), (256, 8), (64, 4), (96, 8)):
+        for C1, g1 in ((0, 0), (64, 4), (64, 8), (256, 8)):
+            for groups in (1, 8, 32):
+                x0 = _cpu_with_totals(C0, g0)
+                x1 = _cpu_with_totals(C1, g1) if C1 else None
+                got = ops._ride_totals(x0, x1, groups)
+                assert (got is not None) == bool(lib.nlc_groupnorm_totals_supported(C0, C1, groups, g0, g1)), (C0, g0, C1, g1, groups)
+                seen.add(got is not None)
+                if got is not None:
+                    assert got[0] is x0._nlc_stats and got[1] == g0 and got[3] == g1 and (got[2] is x1._nlc_stats if C1 else got[2] is None)
+    assert seen == {False, True}
+    x0, x1 = _cpu_with_totals(128, 4), _cpu_with_totals(128, 4)
+    assert ops._ride_totals(x0, x1, 32) is not None
+    assert ops._ride_totals(_cpu_with_totals(128, 4, torch.float32), None, 32) is None                    # f32: totals are a 16-bit matter
+    assert ops._ride_totals(x0, torch.zeros(2, 4, 4, 128, dtype=torch.bfloat16), 32) is None               # a source without totals
+    assert ops._ride_totals(torch.zeros(2, 4, 4, 128, dtype=torch.bfloat16), None, 32) is None
+    monkeypatch.setattr(ops, "FUSED_GN_STATS", False)
+    assert ops._ride_totals(x0, x1, 32) is None
+
+
+def _first_small_map_desc(lib, **gn):
+    """A bf16 descriptor that the small-map kernel takes with gn_in attached and without a workspace (so that nothing but gn_in's own
+    validation stands between nlc_conv2d and the launch), with the given nlc_gn_in fields."""
+    from diffusion_nlc_amd import _ext
+    d, dt = conv_query_desc(2, 8, 8, 64, 128, 3, gn_in=True)
+    q = conv_queries(lib, d, dt)
+    assert q["gn_in_supported"] == 1 and q["workspace_bytes"] == 0
+    spec = _ext.GnIn(**gn)
+    d.gn_in = ctypes.pointer(spec)
+    return d, dt, spec
+
+
+def test_totals_consumers_reject_what_the_rule_rejects():
+    """The four consumers of ride-along totals validate through one function: each rejects a granule of 5, a group size that is no multiple
+    of the granule and stats1 without C1 on the host (NLC_EINVAL, nothing launched - the pointers are host memory), under its own name."""
+    from diffusion_nlc_amd import _ext
+    lib = _ext.load()
+    P, bf16 = _HOST_PTR, _ext.NLC_BF16
+    # (C0, C1, groups, stats1, granule0, granule1, word of the message)
+    bad = [(128, 0, 32, None, 5, 0, b"chunks of (5, 0)"),                   # granule 5
+           (128, 0, 32, None, 8, 0, b"group size 4), chunks of (8, 0)"),    # 4-channel groups, 8-channel chunks
+           (128, 0, 16, P, 4, 4, b"stats1")]                # stats1 without C1
+    for C0, C1, groups, s1, g0, g1, word in bad:
+        assert _totals_rule(C0, C1, groups, g0, g1) == 0 or s1 is not None
+        rc = lib.nlc_groupnorm_prestats(P, None, C0, C1, 2, 64, groups, 1e-5, None, None, None, None, 0, 0, P, bf16, P, g0, s1, g1, None)
+        err = lib.nlc_last_error()
+        assert rc == -1 and b"nlc_groupnorm_prestats" in err and word in err and (s1 is not None or b"granule" in err), err
+        rc = lib.nlc_groupnorm_coef(C0, C1, 2, 64, groups, 1e-5, None, None, None, None, 0, P, g0, s1, g1, P, None)
+        err = lib.nlc_last_error()
+        assert rc == -1 and b"nlc_groupnorm_coef" in err and word in err, err
+        if s1 is None:                                      # (one source only)
+            rc = lib.nlc_groupnorm_pool2x2(P, C0, 2, 8, 8, groups, 1e-5, None, None, None, None, 0, 0, P, P, P, bf16, P, g0, None)
+            err = lib.nlc_last_error()
+            assert rc == -1 and b"nlc_groupnorm_pool2x2" in err and word in err, err
+    for gn, word in ((dict(stats0=P, granule0=5, groups=16), b"chunks of (5, 0)"), (dict(stats0=P, granule0=8, groups=16), b"group size 4), chunks of (8, 0)"),
+                     (dict(stats0=P, stats1=P, granule0=4, granule1=4, groups=8), b"stats1")):
+        d, dt, _keep = _first_small_map_desc(lib, **gn)
+        rc = lib.nlc_conv2d(ctypes.byref(d), dt, None)
+        err = lib.nlc_last_error()
+        assert rc == -1 and b"nlc_conv2d" in err and b"gn_in" in err and word in err, err
+    # the FiLM half is one check too, shared with plain nlc_groupnorm: scale without shift, rows narrower than C
+    assert lib.nlc_groupnorm(P, None, 128, 0, 2, 64, 32, 1e-5, None, None, P, None, 128, 0, P, P, bf16, None) == -1
+    assert b"nlc_groupnorm:" in lib.nlc_last_error() and b"together" in lib.nlc_last_error()
+    assert lib.nlc_groupnorm_prestats(P, None, 128, 0, 2, 64, 32, 1e-5, None, None, P, P, 64, 0, P, bf16, P, 4, None, 0, None) == -1
+    assert b"nlc_groupnorm_prestats" in lib.nlc_last_error() and b"ss_stride" in lib.nlc_last_error()
+
+
+def test_film_stride_is_strict_for_every_groupnorm_shim():
+    """ops._film_stride: f32, rank 2, unit inner stride, at least C wide, one row stride, both or neither - and gn_in_spec / groupnorm_coef
+    reject a malformed pair with the same ValueError instead of handing it to the library."""
+    from diffusion_nlc_amd import ops
+    C = 128
+    row = torch.zeros(2, 2 * C + 8)
+    good = (row[:, :C], row[:, C:2 * C])
+    malformed = [
+        ((good[0].half(), good[1]), "float32"),                          # f16 scale
+        ((row[:, :C - 8], good[1]), "view with unit inner stride"),       # narrower than C
+        ((good[0], torch.zeros(2, C)), "share a row stride"),             # two row strides
+        ((good[0], None), "come together"),                               # scale without shift
+        ((None, good[1]), "come together"),
+        ((row[:, ::2][:, :C], good[1]), "view with unit inner stride"),   # inner stride 2
+    ]
+    assert ops._film_stride(None, None, C, "t") == 0
+    x0 = _cpu_with_totals(C, 4)
+    assert ops._ride_totals(x0, None, 32) is not None
+    for (scale, shift), msg in malformed:
+        with pytest.raises(ValueError, match="t: .*" + msg):
+            ops._film_stride(scale, shift, C, "t")
+        with pytest.raises(ValueError, match="gn_in_spec: .*" + msg):
+            ops.gn_in_spec(x0, None, None, groups=32, eps=1e-5, silu=True, scale=scale, shift=shift)
+        with pytest.raises(ValueError, match="groupnorm_coef: .*" + msg):
+            ops.groupnorm_coef(x0, None, None, groups=32, eps=1e-5, scale=scale, shift=shift)
+    with pytest.raises(ValueError, match="GPU"):                         # a well-formed pair must still be device memory
+        ops._film_stride(*good, C, "t")
+
+
 def test_no_cpu_fallback():
     from diffusion_nlc_amd._ext import NlcError
     eps, sig, _ = build_product("adm_tiny_b")

@@ -1600,3 +1600,59 @@ def test_conv2d_launch_agrees_with_its_queries(case):
         assert ((tot[..., 1] - rq) / rq).abs().max() < 2e-3
     if want_ws:                                      # (every split launch leaves the arrival counters zero)
         assert int(ops._conv_workspace(_dev(), need)[:1024].view(torch.int32).abs().sum()) == 0
+
+
+# (C0, C1, groups) on B = 2, 8 x 8 maps, bf16, every source out of ops.conv2d.  Totals ride along on outputs with Cout % 128 == 0 only, per 4
+# channels for 128 of them and per 8 for 256: the 128- and 256-channel tensors and the 128 + 128 / 128 + 256 (48-channel groups)
+# concatenations are eligible; 64 + 64 and 96 carry no totals and 128 + 256 in 32 groups has 12-channel groups against 8-channel chunks.
+# So of the ineligible cases only (128, 256, 32) reaches nlc_groupnorm_totals_supported with real totals and is rejected by the rule;
+# (64, 64, 32) and (96, 0, 32) stop at the missing totals (their group sizes 4 and 3 are swept against the rule in test_host_cpu.py).
+RIDE_TOTALS_CASES = [(128, 0, 32), (256, 0, 32), (64, 64, 32), (128, 256, 32), (96, 0, 32), (128, 128, 32), (128, 256, 8)]
+RIDE_TOTALS_ELIGIBLE = {(128, 0, 32): (4, 0), (256, 0, 32): (8, 0), (128, 128, 32): (4, 4), (128, 256, 8): (4, 8)}
+
+
+@pytest.mark.parametrize("case", RIDE_TOTALS_CASES, ids=lambda c: "-".join(map(str, c)))
+def test_groupnorm_shims_share_one_totals_rule(case, monkeypatch):
+    """gn_in_spec, groupnorm_coef, groupnorm and groupnorm_pool2x2 take one decision (ops._ride_totals -> nlc_groupnorm_totals_supported):
+    all use the totals or none does; where they do, groupnorm is the nlc_groupnorm_prestats launch on those totals bit for bit and the
+    pooled form agrees with its own statistics pass; where they do not, groupnorm still equals F.group_norm."""
+    from diffusion_nlc_amd import _ext, ops
+    from tests.test_gn_fuzz_gpu import TOL
+    C0, C1, groups = case
+    C, B, H, W, t16 = C0 + C1, 2, 8, 8, torch.bfloat16
+    g = torch.Generator().manual_seed(_seed(case))
+    src = _nhwc(torch.randn(B, 64, H, W, generator=g), t16)
+    def producer(cout):
+        w = torch.randn(cout, 64, 3, 3, generator=g) / 24
+        return ops.conv2d(src, ops.pack_conv(w, torch.randn(cout, generator=g) * 0.3, t16, _dev()))
+    x0 = producer(C0)
+    x1 = producer(C1) if C1 else None
+    gamma = (1 + 0.2 * torch.randn(C, generator=g)).to(_dev())
+    beta = (0.1 * torch.randn(C, generator=g)).to(_dev())
+    ss = (torch.randn(B, 2 * C + 8, generator=g) * 0.3).to(_dev())
+    scale, shift = ss[:, :C], ss[:, C:2 * C]
+    kw = dict(groups=groups, eps=1e-5, x1=x1, scale=scale, shift=shift)
+    tot = ops._ride_totals(x0, x1, groups)
+    assert (tot is not None) == (case in RIDE_TOTALS_ELIGIBLE)
+    assert (ops.gn_in_spec(x0, gamma, beta, silu=True, **kw) is None) == (tot is None)
+    assert (ops.groupnorm_coef(x0, gamma, beta, **kw) is None) == (tot is None)
+    got = ops.groupnorm(x0, gamma, beta, silu=True, **kw)
+    if tot is None:
+        xc = torch.cat([x0.float().cpu()] + ([x1.float().cpu()] if C1 else []), dim=-1).permute(0, 3, 1, 2)
+        ref = F.group_norm(xc, groups, gamma.cpu(), beta.cpu(), eps=1e-5) * (1 + scale.cpu()[:, :, None, None]) + shift.cpu()[:, :, None, None]
+        _close(got.permute(0, 3, 1, 2), F.silu(ref), _tol(t16), "groupnorm without totals")
+        return
+    s0, g0, s1, g1 = tot
+    assert (g0, g1) == RIDE_TOTALS_ELIGIBLE[case] and s0 is ops.ride_stats(x0) and s1 is ops.ride_stats(x1)
+    direct = torch.empty_like(got)
+    _ext.check(_ext.load().nlc_groupnorm_prestats(x0.data_ptr(), ops._ptr(x1), C0, C1, B, H * W, groups, 1e-5, gamma.data_ptr(), beta.data_ptr(),
+                                                  scale.data_ptr(), shift.data_ptr(), ss.stride(0), 1, direct.data_ptr(), ops.dtype_enum(t16),
+                                                  s0.data_ptr(), g0, ops._ptr(s1), g1, ops._stream()), "nlc_groupnorm_prestats")
+    assert torch.equal(got, direct)
+    if x1 is None:
+        pool = lambda: ops.groupnorm_pool2x2(x0, gamma, beta, groups=groups, eps=1e-5, silu=True, scale=scale, shift=shift)
+        h_tot, x_tot = pool()
+        monkeypatch.setattr(ops, "FUSED_GN_STATS", False)
+        h_pass, x_pass = pool()
+        assert torch.equal(x_tot, x_pass)
+        _close(h_tot, h_pass.float().cpu(), TOL[t16], "pooled GroupNorm: totals vs statistics pass")
