@@ -12,15 +12,16 @@ attention head, skip_scale sqrt(1/2), GroupNorm(min(32,C/4) groups, eps 1e-6).
 """
 from __future__ import annotations
 
-import math
+from types import SimpleNamespace
 from typing import Optional
 
 import numpy as np
 import torch
 
 from . import ops
-from ._ext import ACT_NONE, ACT_SILU
-from .hipnet import EmbBank, HipModule, Norm, SigmaHead, SpecBuilder, as_f32_cuda, first_conv_weight, pack
+from ._ext import ACT_SILU
+from .hipnet import (EmbBank, HipModule, Norm, ResBlock, SelfAttention, SigmaNet, SpecBuilder, as_f32_cuda, first_conv_weight, pack, pack_opt,
+                     qkv_row_scale)
 
 GN_EPS = 1e-6
 SKIP_SCALE = float(np.sqrt(0.5))
@@ -44,69 +45,36 @@ def _spec_block(sb: SpecBuilder, p, cin, cout, emb_ch, attention, up=False, down
         if up or down:
             sb.add(p + ".skip.resample_filter", (1, 1, 2, 2))
     if attention:
-        sb.norm(p + ".norm2", cout)
-        sb.conv(p + ".qkv", 3 * cout, cout, 1)
-        sb.conv(p + ".proj", cout, cout, 1)
+        _spec_attention(sb, p, cout)
 
 
-class _UNetBlock:
-    def __init__(self, sd, p, dtype, device, bank: Optional[EmbBank], attention: bool, up=False, down=False, pure=False):
-        cin = sd[p + ".norm0.weight"].shape[0]
-        cout = sd[p + ".conv0.weight"].shape[0]
-        self.n0 = Norm(sd, p + ".norm0", device, _groups(cin), GN_EPS)
-        self.c0 = pack(sd, p + ".conv0", dtype, device)
-        self.n1 = Norm(sd, p + ".norm1", device, _groups(cout), GN_EPS)
-        self.c1 = pack(sd, p + ".conv1", dtype, device)
-        self.skip = pack(sd, p + ".skip", dtype, device) if (p + ".skip.weight") in sd else None
-        self.up, self.down, self.pure = up, down, pure
-        self.emb_off = bank.add(sd[p + ".affine.weight"], sd[p + ".affine.bias"])[0] if bank is not None else None
-        self.attn = None
-        if attention:
-            c = cout
-            idx = torch.arange(3 * c)
-            s_, c_ = idx // c, idx % c
-            perm = c_ * 3 + s_                      # reshape(n, C, 3, T).unbind(2): channel = c*3 + {q,k,v} (:199-200)
-            scale = torch.ones(3 * c, dtype=torch.float64)
-            scale[: 2 * c] = float(c) ** -0.25      # k / sqrt(C) (:127) split evenly over q and k
-            f, self.base2 = ops.attention_logit_scale(dtype)
-            scale[:c] *= f
-            self.attn = (Norm(sd, p + ".norm2", device, _groups(c), GN_EPS),
-                         pack(sd, p + ".qkv", dtype, device, row_perm=perm, row_scale=scale),
-                         pack(sd, p + ".proj", dtype, device))
+def _spec_attention(sb: SpecBuilder, p, c):
+    sb.norm(p + ".norm2", c)
+    sb.conv(p + ".qkv", 3 * c, c, 1)
+    sb.conv(p + ".proj", c, c, 1)
 
-    def __call__(self, x, x1, emb_all):
-        both = None
-        if self.skip is not None and not self.down and not self.up:
-            both = self.n0.with_skip(x, self.skip, silu=True, x1=x1)                # norm0 and the skip projection from one read
-        emb = None if self.emb_off is None else emb_all[:, self.emb_off:]
-        res = None
-        if both is not None:
-            hn, res = both
-            h = ops.conv2d(hn, self.c0, emb=emb)
-        elif self.down:
-            h = ops.conv2d(ops.avgpool2x2(self.n0(x, silu=True, x1=x1)), self.c0, emb=emb)
-        else:                              # (small maps: the normalisation is applied by the convolution itself, hipnet.Norm.then_conv)
-            h = self.n0.then_conv(x, self.c0, silu=True, x1=x1, upsample2x=self.up, emb=emb)
-        # PureUNetBlock.forward feeds conv0's output straight into conv1 (src/edm_networks.py:944-945)
-        if res is not None:
-            pass
-        elif self.skip is not None:
-            xs, xs1 = x, x1
-            if self.down:
-                xs = ops.avgpool2x2(x)
-            res = ops.conv2d(xs, self.skip, x1=xs1, upsample2x=self.up)
-        else:
-            res = x
-        if self.pure:
-            x = ops.conv2d(h, self.c1, res=res, out_scale=SKIP_SCALE)
-        else:
-            x = self.n1.then_conv(h, self.c1, silu=True, res=res, out_scale=SKIP_SCALE)
-        if self.attn is not None:
-            norm, qkv, proj = self.attn
-            B, H, W, C = x.shape
-            a = ops.attention(ops.conv2d(norm(x, silu=False), qkv).view(B, H * W, 3 * C), 1, base2=self.base2)
-            x = ops.conv2d(a.view(B, H, W, C), proj, res=x, out_scale=SKIP_SCALE)
-        return x
+
+def _unet_block(sd, p, dtype, device, bank: Optional[EmbBank], up=False, down=False, pure=False) -> ResBlock:
+    """UNetBlock without its attention (src/edm_networks.py:183-197); ``pure``: PureUNetBlock.forward feeds conv0's output straight into
+    conv1 (:944-945).  An up / down block always has the skip 1x1 (:176): up reads x through that launch's folded upsample.  Known
+    difference from ADM: the down block does not use the fused pool (``fused_pool`` stays off) - norm -> pool -> conv and a second pool
+    of x for the skip; switching it would change 16-bit results, so it is not this block's to fix."""
+    cin, cout = sd[p + ".norm0.weight"].shape[0], sd[p + ".conv0.weight"].shape[0]
+    return ResBlock(Norm(sd, p + ".norm0", device, _groups(cin), GN_EPS), pack(sd, p + ".conv0", dtype, device),
+                    None if pure else Norm(sd, p + ".norm1", device, _groups(cout), GN_EPS), pack(sd, p + ".conv1", dtype, device),
+                    pack_opt(sd, p + ".skip", dtype, device),
+                    None if bank is None else bank.add(sd[p + ".affine.weight"], sd[p + ".affine.bias"])[0],
+                    up=up, down=down, out_scale=SKIP_SCALE)
+
+
+def _attention(sd, p, dtype, device) -> SelfAttention:
+    """The attention half of a UNetBlock (:198-203), keys under the block's own prefix."""
+    c = sd[p + ".proj.weight"].shape[0]
+    idx = torch.arange(3 * c)
+    perm = (idx % c) * 3 + idx // c             # reshape(n, C, 3, T).unbind(2): channel = c*3 + {q,k,v} (:199-200)
+    scale, base2 = qkv_row_scale(c, float(c) ** -0.25, dtype)      # k / sqrt(C) (:127) split evenly over q and k
+    return SelfAttention(Norm(sd, p + ".norm2", device, _groups(c), GN_EPS), pack(sd, p + ".qkv", dtype, device, row_perm=perm, row_scale=scale),
+                         pack(sd, p + ".proj", dtype, device), 1, base2, out_scale=SKIP_SCALE)
 
 
 class SongUNet(HipModule):
@@ -177,7 +145,7 @@ class SongUNet(HipModule):
         return sb.spec
 
     def _build(self, sd, device, dtype):
-        P = type("Plan", (), {})()
+        P = SimpleNamespace()
         half = self.model_channels // 2
         fr = torch.arange(0, half, dtype=torch.float32) / (half - 1)         # endpoint=True (:220-222)
         P.freqs = ((1 / 10000) ** fr).to(device)
@@ -186,18 +154,22 @@ class SongUNet(HipModule):
         bank = EmbBank()
         enc, dec = self._layout()
         P.enc, P.dec = [], []
+
+        def block(p, kw):                       # (UNetBlock's two halves: residual block, attention or None)
+            return (_unet_block(sd, p, dtype, device, bank, up=kw.get("up", False), down=kw.get("down", False)),
+                    _attention(sd, p, dtype, device) if kw.get("attention") else None)
         for p, kind, cin, cout, kw in enc:
             if kind == "conv":
                 P.enc.append(("conv",) + first_conv_weight(sd, p, device))
             else:
-                P.enc.append(("block", _UNetBlock(sd, p, dtype, device, bank, kw.get("attention", False), down=kw.get("down", False))))
+                P.enc.append(("block",) + block(p, kw))
         for p, kind, cin, cout, kw in dec:
             if kind == "aux_norm":
                 P.aux_norm = Norm(sd, p, device, _groups(cin), GN_EPS)
             elif kind == "aux_conv":
                 P.aux_conv = pack(sd, p, dtype, device)
             else:
-                P.dec.append((bool(kw.get("cat")), _UNetBlock(sd, p, dtype, device, bank, kw.get("attention", False), up=kw.get("up", False))))
+                P.dec.append((bool(kw.get("cat")),) + block(p, kw))
         bank.finalize(device, allow_split=ops.is16(dtype))
         P.bank = bank
         return P
@@ -217,11 +189,15 @@ class SongUNet(HipModule):
                     x = ops.conv_first(x_nchw, item[1], item[2], self.compute_dtype, in_scale=in_scale)
                 else:
                     x = item[1](x, None, emb_all)
+                    if item[2] is not None:
+                        x = item[2](x)
                 skips.append(x)
             if mode == "encode":
                 return x if feat_nhwc else ops.nhwc_to_nchw_f32(x)
-            for cat, blk in P.dec:
+            for cat, blk, attn in P.dec:
                 x = blk(x, skips.pop() if cat else None, emb_all)
+                if attn is not None:
+                    x = attn(x)
             return ops.conv2d(P.aux_norm(x, silu=True), P.aux_conv, out_nchw_f32=True)
 
     def _prep(self, x, noise_labels):
@@ -237,59 +213,24 @@ class SongUNet(HipModule):
         return self.run(*self._prep(x, noise_labels), mode="encode")
 
 
-class SigmaModel(HipModule):
+class SigmaModel(SigmaNet):
     """src/edm_networks.py:979-1022: PureUNetBlock (attention on even blocks) + pad/conv-s2 downsample, SiLU head."""
 
+    ATTENTION_OWN_INDEX = False
+    HEAD_ACT = ACT_SILU
+
     def __init__(self, dim=4, channels=64, n_blocks=2, out_dim=1, dropout=0.1, resample_filter=[1, 1]):
-        if out_dim != 1:
-            raise NotImplementedError("SigmaModel: out_dim must be 1")
-        self.dim, self.channels, self.n_blocks = dim, channels, n_blocks
-        super().__init__()
+        super().__init__(dim, channels, n_blocks, out_dim)
 
-    def _layout(self):
-        out, idx, d = [], 0, self.dim
-        for i in range(self.n_blocks):
-            pad = d % 2 != 0
-            if pad:
-                d += 1
-            idx += 1
-            blk = f"down_layer.{idx}"; idx += 1
-            down = f"down_layer.{idx}"; idx += 1
-            d //= 2
-            out.append((pad, blk, i % 2 == 0, down))
-        return out, d
+    def _has_attention(self, i):
+        return i % 2 == 0
 
-    def param_spec(self):
-        sb = SpecBuilder()
-        c = self.channels
-        layout, d = self._layout()
-        for pad, blk, attn, down in layout:
-            _spec_block(sb, blk, c, c, 0, attn)
-            sb.conv(down + ".conv", c, c, 3)
-        sb.linear("fc_layer.1", 128, c * d * d)
-        sb.batchnorm("fc_layer.2", 128)
-        sb.linear("final_mlp", 1, 128)
-        return sb.spec
+    def _spec_block(self, sb, p, c):
+        _spec_block(sb, p, c, c, 0, False)
 
-    def _build(self, sd, device, dtype):
-        P = type("Plan", (), {})()
-        layout, _ = self._layout()
-        P.blocks = [(pad, _UNetBlock(sd, blk, dtype, device, None, attn, pure=True), pack(sd, down + ".conv", dtype, device))
-                    for pad, blk, attn, down in layout]
-        P.head = SigmaHead(sd, device, ACT_SILU, allow_split=ops.is16(dtype))
-        return P
+    _spec_attention = staticmethod(_spec_attention)
 
-    def run_nhwc(self, h):
-        P = self.plan()
-        with torch.cuda.device(self.device):
-            for pad, blk, down in P.blocks:
-                if pad:
-                    h = ops.pad_rb(h)
-                h = blk(h, None, None)
-                h = ops.conv2d(h, down, stride=2, pad=(0, 0), out_hw=(h.shape[1] // 2, h.shape[2] // 2))
-            return P.head(h)
+    def _make_block(self, sd, p, dtype, device):
+        return _unet_block(sd, p, dtype, device, None, pure=True)
 
-    def forward(self, feat):
-        self._require_gpu()
-        h = ops.nchw_f32_to_nhwc(as_f32_cuda(feat, self.device), self.compute_dtype)
-        return self.run_nhwc(h).view(-1, 1, 1, 1)
+    _make_attention = staticmethod(_attention)

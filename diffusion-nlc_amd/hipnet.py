@@ -21,6 +21,7 @@ from __future__ import annotations
 import functools
 import math
 from collections import OrderedDict
+from types import SimpleNamespace
 from typing import Dict, Iterable, List, Optional, Tuple
 
 import torch
@@ -281,6 +282,15 @@ class HipModule:
             raise NlcError(f"{type(self).__name__} runs on the HIP kernels only: move it to a GPU with .to('cuda:0') "
                            "(there is no CPU fallback; the CPU restatement lives in oracle/ for tests)")
 
+    def _prep(self, x, t):
+        """The arguments of a network called as ``model(x, t)``: f32 on the device, t one value per image."""
+        self._require_gpu()
+        x = as_f32_cuda(x, self.device)
+        t = as_f32_cuda(t, self.device).reshape(-1)
+        if t.numel() == 1 and x.shape[0] > 1:
+            t = t.expand(x.shape[0]).contiguous()
+        return x, t
+
     def plan(self):
         # the packed weights bake ops.ATTN_BASE2 in (log2(e) folded into the q rows): a flip re-packs
         if self._plan is not None and self.__dict__.get("_plan_base2") != ops.ATTN_BASE2:
@@ -337,18 +347,23 @@ class Norm:
         res, hn = ops.conv2d(x, pw_skip, x1=x1, gn_coef=coef, gn_act=ACT_SILU if silu else ACT_NONE, norm_out=True, emit_stats=False)
         return hn, res
 
+    # what of a launch's keywords its two queries are shown: the geometry, and for the small-map kernel also the residual's form and the
+    # bias / embedding rows (it reads them as 16-byte vectors: the query sees the pointers the launch will see, so an embedding view at
+    # an odd offset or row stride takes the separate pass instead of aborting the launch)
+    PROLOGUE_QUERY_KEYS = frozenset(("stride", "pad", "out_hw", "upsample2x", "out_nchw_f32"))
+    GN_IN_QUERY_KEYS = PROLOGUE_QUERY_KEYS | {"res_upsample2x", "emb", "use_bias"}
+
     def then_conv(self, x, pw, *, silu: bool, x1=None, scale=None, shift=None, **conv_kw):
         """conv(act(norm(cat(x, x1)))) - with the normalisation applied inside the convolution's LDS prologue when the launch
         supports it and the statistics rode along with x (x1), else as the separate GroupNorm pass followed by the conv."""
-        geom = {k: v for k, v in conv_kw.items() if k in ("stride", "pad", "out_hw", "upsample2x", "out_nchw_f32", "res_upsample2x")}
-        # (the small-map kernel reads bias and embedding rows as 16-byte vectors: the query sees the pointers the launch will see, so
-        #  an embedding view at an odd offset or row stride takes the separate pass instead of aborting the launch)
-        asked = {k: v for k, v in conv_kw.items() if k in ("emb", "use_bias")}
-        if ops.FUSE_GN_SMALL and not geom.get("res_upsample2x") and not geom.get("upsample2x") and ops.conv2d(x, pw, x1=x1, query_gn_in=True, **geom, **asked):
+        shown = lambda keys: {k: v for k, v in conv_kw.items() if k in keys}
+        if ops.FUSE_GN_SMALL and not conv_kw.get("res_upsample2x") and not conv_kw.get("upsample2x") \
+                and ops.conv2d(x, pw, x1=x1, query_gn_in=True, **shown(self.GN_IN_QUERY_KEYS)):
             spec = ops.gn_in_spec(x, self.gamma, self.beta, groups=self.groups, eps=self.eps, silu=silu, x1=x1, scale=scale, shift=shift)
             if spec is not None:
                 return ops.conv2d(x, pw, x1=x1, gn_in=spec, **conv_kw)
-        if (ops.FUSE_GN_CONV or (ops.FUSE_GN_CONV_NT1 and pw.Cout <= ops.FUSE_GN_CONV_MAXC)) and ops.conv2d(x, pw, x1=x1, query_prologue=True, **{k: v for k, v in conv_kw.items() if k in ("stride", "pad", "out_hw", "upsample2x", "out_nchw_f32")}):
+        if (ops.FUSE_GN_CONV or (ops.FUSE_GN_CONV_NT1 and pw.Cout <= ops.FUSE_GN_CONV_MAXC)) \
+                and ops.conv2d(x, pw, x1=x1, query_prologue=True, **shown(self.PROLOGUE_QUERY_KEYS)):
             coef = ops.groupnorm_coef(x, self.gamma, self.beta, groups=self.groups, eps=self.eps, x1=x1, scale=scale, shift=shift)
             if coef is not None:
                 return ops.conv2d(x, pw, x1=x1, gn_coef=coef, gn_act=ACT_SILU if silu else ACT_NONE, **conv_kw)
@@ -414,6 +429,87 @@ class EmbBank:
         return ops.conv2d(emb_in, self.packed, allow_split=getattr(self, "allow_split", False))
 
 
+def pack_opt(sd, p, spec, device) -> Optional[ops.PackedConv]:
+    """A layer that only some blocks have (the skip projection of a block that changes its channel count)."""
+    return pack(sd, p, spec, device) if (p + ".weight") in sd else None
+
+
+class ResBlock:
+    """norm -> conv 1 (+embedding) -> [norm (FiLM)] -> conv 2 (+skip), the residual block of all three families - and the ONE place that
+    picks its fused forms.  The families build it from ready parts (their own state-dict keys, GroupNorm groups / eps) and these flags:
+
+    ``emb_off``    row offset of this block's embedding projection in the network's EmbBank (None: no embedding, the sigma nets)
+    ``film``       the embedding is (scale, shift) of the second norm instead of an addend of conv 1 (ADM ``use_scale_shift_norm``)
+    ``up``         conv 1 reads its input nearest-2x upsampled; the skip is the block's 1x1 with the upsample folded into its gather
+                   (EDM), or without one the input itself, upsampled by conv 2's epilogue (``res_upsample2x``, ADM: always ch -> ch)
+    ``down``       both branches are 2x2-mean pooled.  ``fused_pool`` (ADM): ``Norm.pooled`` gives both from one read of x.  EDM's down
+                   block stays norm -> pool -> conv with its skip 1x1 on a pool of x made afterwards: a known difference between the
+                   families, kept because the fused pool would change EDM's 16-bit results
+    ``n2 is None`` conv 2 reads conv 1's output as it is (EDM's PureUNetBlock, sigma net)
+    ``out_scale``  of conv 2's epilogue, after the skip is added (EDM: sqrt(1/2))
+    """
+
+    def __init__(self, n1: Norm, c1, n2: Optional[Norm], c2, skip=None, emb_off: Optional[int] = None, *, up=False, down=False,
+                 film=False, fused_pool=False, out_scale=1.0):
+        self.n1, self.c1, self.n2, self.c2, self.skip, self.emb_off = n1, c1, n2, c2, skip, emb_off
+        self.up, self.down, self.fused_pool, self.out_scale = up, down, fused_pool, out_scale
+        self.film = film and emb_off is not None
+
+    def __call__(self, x, x1, emb_all):
+        emb = None if self.emb_off is None else emb_all[:, self.emb_off:]
+        c1_emb = None if self.film else emb
+        res = None
+        if self.down:
+            if x1 is not None:
+                raise NotImplementedError("down-sampling ResBlock on a concatenated input (the reference has none)")
+            if self.fused_pool:                                # one read of x for both branches, no full-resolution h
+                h, xp = self.n1.pooled(x, silu=True)
+                h = ops.conv2d(h, self.c1, emb=c1_emb)
+            else:
+                h = ops.conv2d(ops.avgpool2x2(self.n1(x, silu=True)), self.c1, emb=c1_emb)
+                xp = ops.avgpool2x2(x)
+            x = xp
+        else:
+            both = self.n1.with_skip(x, self.skip, silu=True, x1=x1) if (self.skip is not None and not self.up) else None
+            if both is not None:                               # norm 1 and the skip projection from one read of x
+                hn, res = both
+                h = ops.conv2d(hn, self.c1, emb=c1_emb)
+            else:                                              # gn_in on small maps, the LDS prologue, or the separate pass
+                h = self.n1.then_conv(x, self.c1, silu=True, x1=x1, upsample2x=self.up, emb=c1_emb)
+        if res is None:
+            res = x if self.skip is None else ops.conv2d(x, self.skip, x1=x1, upsample2x=self.up)
+        tail = dict(res=res, res_upsample2x=self.up and self.skip is None, out_scale=self.out_scale)
+        if self.n2 is None:
+            return ops.conv2d(h, self.c2, **tail)
+        if self.film:
+            cout = self.c1.Cout
+            tail.update(scale=emb[:, :cout], shift=emb[:, cout:2 * cout])
+        return self.n2.then_conv(h, self.c2, silu=True, **tail)
+
+
+def qkv_row_scale(c: int, qk: float, spec) -> Tuple[torch.Tensor, bool]:
+    """(f64 scale of the 3c packed [q|k|v] rows, base2): ``qk`` - the family's own split of the logit scale - on q and k, and on q also
+    log2(e) when the attention kernel of this compute spec works in base 2 (``base2``)."""
+    scale = torch.ones(3 * c, dtype=torch.float64)
+    scale[: 2 * c] = qk
+    f, base2 = ops.attention_logit_scale(spec)
+    scale[:c] *= f
+    return scale, base2
+
+
+class SelfAttention:
+    """GroupNorm -> 1x1 qkv (rows already [q|k|v][head][ch] and scaled, see qkv_row_scale) -> flash attention -> 1x1 proj (+x) * out_scale."""
+
+    def __init__(self, norm: Norm, qkv, proj, heads: int, base2: bool, out_scale: float = 1.0):
+        self.norm, self.qkv, self.proj, self.heads, self.base2, self.out_scale = norm, qkv, proj, heads, base2, out_scale
+
+    def __call__(self, x):
+        B, H, W, C = x.shape
+        qkv = ops.conv2d(self.norm(x, silu=False), self.qkv)
+        a = ops.attention(qkv.view(B, H * W, 3 * C), self.heads, base2=self.base2)
+        return ops.conv2d(a.view(B, H, W, C), self.proj, res=x, out_scale=self.out_scale)
+
+
 class SigmaHead:
     """Flatten -> Linear -> BatchNorm1d(eval) -> act -> Linear, all f32 (src/unet_adm.py:1051-1058,1078-1083).
 
@@ -436,6 +532,86 @@ class SigmaHead:
         flat = ops.nhwc_to_nchw_f32(h_nhwc).view(h_nhwc.shape[0], -1)
         h = ops.conv2d(flat, self.fc, act=self.act, allow_split=self.allow_split)
         return ops.conv2d(h, self.final).view(-1)          # r[b]
+
+
+class SigmaNet(HipModule):
+    """The sigma net of all three families: n_blocks x [(pad to even) -> residual block -> (attention) -> 3x3 stride-2 conv], then the
+    f32 head.  A family supplies its constructor, ``_spec_block`` / ``_spec_attention`` (state-dict keys) and ``_make_block`` / ``_make_attention``
+    (the modules), and may change what is below."""
+
+    DOWN_KEY = ".conv"              # key suffix of the down-sampling conv under its down_layer index
+    ATTENTION_OWN_INDEX = True      # attention is a down_layer entry of its own - or part of the block's entry (EDM)
+    HEAD_ACT = ACT_GELU
+
+    def __init__(self, dim, channels, n_blocks, out_dim):
+        if out_dim != 1:
+            raise NotImplementedError("SigmaModel: out_dim must be 1")
+        self.dim, self.channels, self.n_blocks = dim, channels, n_blocks
+        super().__init__()
+
+    def _has_attention(self, i: int) -> bool:
+        return i == 0
+
+    def _downsample(self, h, pw):
+        """pad (0,1,0,1) + conv s2 p0, the pad folded into the gather."""
+        return ops.conv2d(h, pw, stride=2, pad=(0, 0), out_hw=(h.shape[1] // 2, h.shape[2] // 2))
+
+    def _layout(self):
+        """[(pad, block key, attention key or None, down key)], and the side of the map the head flattens."""
+        out, idx, d = [], 0, self.dim
+        for i in range(self.n_blocks):
+            pad = d % 2 != 0
+            if pad:
+                d += 1
+            idx += 1                                   # (the pad / identity entry has no parameters)
+            res = f"down_layer.{idx}"; idx += 1
+            attn = None
+            if self._has_attention(i):
+                attn = res
+                if self.ATTENTION_OWN_INDEX:
+                    attn = f"down_layer.{idx}"; idx += 1
+            down = f"down_layer.{idx}"; idx += 1
+            d //= 2
+            out.append((pad, res, attn, down + self.DOWN_KEY))
+        return out, d
+
+    def param_spec(self):
+        sb = SpecBuilder()
+        c = self.channels
+        layout, d = self._layout()
+        for pad, res, attn, down in layout:
+            self._spec_block(sb, res, c)
+            if attn:
+                self._spec_attention(sb, attn, c)
+            sb.conv(down, c, c, 3)
+        sb.linear("fc_layer.1", 128, c * d * d)
+        sb.batchnorm("fc_layer.2", 128)
+        sb.linear("final_mlp", 1, 128)
+        return sb.spec
+
+    def _build(self, sd, device, dtype):
+        blocks = [(pad, self._make_block(sd, res, dtype, device), self._make_attention(sd, attn, dtype, device) if attn else None,
+                   pack(sd, down, dtype, device)) for pad, res, attn, down in self._layout()[0]]
+        return SimpleNamespace(blocks=blocks, head=SigmaHead(sd, device, self.HEAD_ACT, allow_split=ops.is16(dtype)))
+
+    def run_nhwc(self, h: torch.Tensor) -> torch.Tensor:
+        """feat NHWC (compute dtype) -> r[b] f32."""
+        P = self.plan()
+        with torch.cuda.device(self.device):
+            for pad, res, attn, down in P.blocks:
+                if pad:
+                    h = ops.pad_rb(h)
+                h = res(h, None, None)
+                if attn is not None:
+                    h = attn(h)
+                h = self._downsample(h, down)
+            return P.head(h)
+
+    def forward(self, feat):
+        """feat: NCHW f32 as the reference passes it -> (B,1,1,1) f32."""
+        self._require_gpu()
+        h = ops.nchw_f32_to_nhwc(as_f32_cuda(feat, self.device), self.compute_dtype)
+        return self.run_nhwc(h).view(-1, 1, 1, 1)
 
 
 def first_conv_weight(sd, p, device):

@@ -18,13 +18,15 @@ kernel from libnlc_hip.so:
 from __future__ import annotations
 
 import math
+from types import SimpleNamespace
 from typing import List, Optional, Tuple
 
 import torch
 
 from . import ops
-from ._ext import ACT_GELU, ACT_NONE, ACT_SILU
-from .hipnet import EmbBank, HipModule, Norm, SigmaHead, SpecBuilder, as_f32_cuda, first_conv_weight, f32, pack
+from ._ext import ACT_SILU
+from .hipnet import (EmbBank, HipModule, Norm, ResBlock, SelfAttention, SigmaNet, SpecBuilder, first_conv_weight, f32, pack, pack_opt,
+                     qkv_row_scale)
 
 GN_GROUPS, GN_EPS = 32, 1e-5       # GroupNorm32 (src/nn_util.py:93-100)
 
@@ -50,77 +52,29 @@ def _spec_attention(sb: SpecBuilder, p, ch):
     sb.conv(p + ".proj_out", ch, ch, 1, dims=1)
 
 
-class _ResBlock:
-    def __init__(self, sd, p, dtype, device, bank: Optional[EmbBank], scale_shift: bool, up=False, down=False):
-        self.n1 = Norm(sd, p + ".in_layers.0", device, GN_GROUPS, GN_EPS)
-        self.c1 = pack(sd, p + ".in_layers.2", dtype, device)
-        self.n2 = Norm(sd, p + ".out_layers.0", device, GN_GROUPS, GN_EPS)
-        self.c2 = pack(sd, p + ".out_layers.3", dtype, device)
-        self.skip = pack(sd, p + ".skip_connection", dtype, device) if (p + ".skip_connection.weight") in sd else None
-        self.up, self.down, self.scale_shift = up, down, scale_shift
-        self.cout = self.c1.Cout
-        self.emb_off = None
-        if bank is not None:
-            self.emb_off, _ = bank.add(sd[p + ".emb_layers.1.weight"], sd[p + ".emb_layers.1.bias"])
-
-    def __call__(self, x, x1, emb_all):
-        emb = None if self.emb_off is None else emb_all[:, self.emb_off:]
-        c1_emb = None if (self.scale_shift or emb is None) else emb                      # h + emb_out (:254)
-        if self.down:                                          # AvgPool2d on both branches (:193-195): norm, then pool, then conv
-            if x1 is not None:
-                raise NotImplementedError("down-sampling ResBlock on a concatenated input (the reference has none)")
-            h, x = self.n1.pooled(x, silu=True)                # one read of x for both branches, no full-resolution h
-            h = ops.conv2d(h, self.c1, emb=c1_emb)
-        res = None
-        if not self.down:
-            both = self.n1.with_skip(x, self.skip, silu=True, x1=x1) if (self.skip is not None and not self.up) else None
-            if both is not None:                               # in_layers(x) and skip_connection(x) (:236, :256) from one read of x
-                hn, res = both
-                h = ops.conv2d(hn, self.c1, emb=c1_emb)
-            else:                                              # GroupNorm+SiLU applied inside the conv's LDS prologue when it can be
-                h = self.n1.then_conv(x, self.c1, silu=True, x1=x1, upsample2x=self.up, emb=c1_emb)
-        res_ups = False
-        if self.up and self.skip is None:
-            res_ups = True                                     # x_upd(x): read nearest-2x upsampled by the conv's epilogue, never materialised
-        elif self.up:
-            x = ops.upsample2x(x)
-        if res is not None:
-            pass
-        elif self.skip is not None:
-            res = ops.conv2d(x, self.skip, x1=x1)
-        else:
-            res = x
-        if self.scale_shift and emb is not None:
-            return self.n2.then_conv(h, self.c2, silu=True, scale=emb[:, :self.cout], shift=emb[:, self.cout:2 * self.cout], res=res,
-                                     res_upsample2x=res_ups)
-        return self.n2.then_conv(h, self.c2, silu=True, res=res, res_upsample2x=res_ups)
+def _resblock(sd, p, dtype, device, bank: Optional[EmbBank], scale_shift: bool, up=False, down=False) -> ResBlock:
+    """ResBlock (src/unet_adm.py:236-256): h + emb_out (:254) or FiLM on the second norm; ``resblock_updown`` blocks are ch -> ch, so an
+    up block's skip is x_upd(x) itself and a down block's the pooled x (AvgPool2d on both branches, :193-195)."""
+    norm = lambda q: Norm(sd, p + q, device, GN_GROUPS, GN_EPS)
+    return ResBlock(norm(".in_layers.0"), pack(sd, p + ".in_layers.2", dtype, device),
+                    norm(".out_layers.0"), pack(sd, p + ".out_layers.3", dtype, device), pack_opt(sd, p + ".skip_connection", dtype, device),
+                    None if bank is None else bank.add(sd[p + ".emb_layers.1.weight"], sd[p + ".emb_layers.1.bias"])[0],
+                    up=up, down=down, film=scale_shift, fused_pool=True)
 
 
-class _Attention:
-    def __init__(self, sd, p, dtype, device, heads: int, new_order: bool):
-        ch3 = sd[p + ".qkv.weight"].shape[0]
-        c = ch3 // 3
-        d = c // heads
-        self.heads = heads
-        self.norm = Norm(sd, p + ".norm", device, GN_GROUPS, GN_EPS)
-        idx = torch.arange(ch3)
-        if new_order:                        # [q|k|v][head][ch] already canonical (:380-388)
-            perm = idx
-        else:                                # legacy [head][q|k|v][ch] (:347) -> [q|k|v][head][ch]
-            s_, h_, c_ = idx // (heads * d), (idx // d) % heads, idx % d
-            perm = h_ * (3 * d) + s_ * d + c_
-        scale = torch.ones(ch3, dtype=torch.float64)
-        scale[: 2 * c] = 1.0 / math.sqrt(math.sqrt(d))      # q and k each scaled by ch^-1/4 (:348-351)
-        f, self.base2 = ops.attention_logit_scale(dtype)
-        scale[:c] *= f                                       # 16-bit models: log2(e) rides along on q, the kernel uses 2^x
-        self.qkv = pack(sd, p + ".qkv", dtype, device, row_perm=perm, row_scale=scale)
-        self.proj = pack(sd, p + ".proj_out", dtype, device)
-
-    def __call__(self, x):
-        B, H, W, C = x.shape
-        qkv = ops.conv2d(self.norm(x, silu=False), self.qkv)
-        a = ops.attention(qkv.view(B, H * W, 3 * C), self.heads, base2=self.base2)
-        return ops.conv2d(a.view(B, H, W, C), self.proj, res=x)
+def _attention(sd, p, dtype, device, heads: int, new_order: bool) -> SelfAttention:
+    ch3 = sd[p + ".qkv.weight"].shape[0]
+    c = ch3 // 3
+    d = c // heads
+    idx = torch.arange(ch3)
+    if new_order:                        # [q|k|v][head][ch] already canonical (:380-388)
+        perm = idx
+    else:                                # legacy [head][q|k|v][ch] (:347) -> [q|k|v][head][ch]
+        s_, h_, c_ = idx // (heads * d), (idx // d) % heads, idx % d
+        perm = h_ * (3 * d) + s_ * d + c_
+    scale, base2 = qkv_row_scale(c, 1.0 / math.sqrt(math.sqrt(d)), dtype)      # q and k each scaled by ch^-1/4 (:348-351)
+    return SelfAttention(Norm(sd, p + ".norm", device, GN_GROUPS, GN_EPS), pack(sd, p + ".qkv", dtype, device, row_perm=perm, row_scale=scale),
+                         pack(sd, p + ".proj_out", dtype, device), heads, base2)
 
 
 class UNetModel(HipModule):
@@ -225,7 +179,7 @@ class UNetModel(HipModule):
 
     # ---- device plan ---------------------------------------------------------------------------
     def _build(self, sd, device, dtype):
-        P = type("Plan", (), {})()
+        P = SimpleNamespace()
         blocks_in, mid, blocks_out, ch_last, E = self._layout()
         half = self.model_channels // 2
         # frequency table computed exactly as timestep_embedding does (src/nn_util.py:113-116)
@@ -241,10 +195,10 @@ class UNetModel(HipModule):
                 if kind == "conv_in":
                     out.append(("conv_in",) + first_conv_weight(sd, p, device))
                 elif kind == "res":
-                    out.append(("res", _ResBlock(sd, p, dtype, device, bank, self.use_scale_shift_norm,
+                    out.append(("res", _resblock(sd, p, dtype, device, bank, self.use_scale_shift_norm,
                                                  up=kw.get("up", False), down=kw.get("down", False))))
                 elif kind == "attn":
-                    out.append(("attn", _Attention(sd, p, dtype, device, kw["heads"], self.use_new_attention_order)))
+                    out.append(("attn", _attention(sd, p, dtype, device, kw["heads"], self.use_new_attention_order)))
                 elif kind == "downsample":
                     out.append(("downsample", pack(sd, p + ".op", dtype, device) if self.conv_resample else None))
                 elif kind == "upsample":
@@ -321,14 +275,6 @@ class UNetModel(HipModule):
                 return out
             return out, (feat if feat_nhwc else ops.nhwc_to_nchw_f32(feat))
 
-    def _prep(self, x, timesteps):
-        self._require_gpu()
-        x = as_f32_cuda(x, self.device)
-        t = as_f32_cuda(timesteps, self.device).reshape(-1)
-        if t.numel() == 1 and x.shape[0] > 1:
-            t = t.expand(x.shape[0]).contiguous()
-        return x, t
-
     def _labels(self, y, n):
         if y is None:
             return None
@@ -349,77 +295,29 @@ class UNetModel(HipModule):
         return self.run(x, t, mode="both", y=self._labels(y, x.shape[0]))
 
 
-class SigmaModel(HipModule):
+class SigmaModel(SigmaNet):
     """src/unet_adm.py:1029-1083: (pad) -> PureResNetBlock -> [Attention on block 0] -> conv s2 p1, then the f32 head."""
+
+    DOWN_KEY = ".op"
 
     def __init__(self, dim=4, channels=64, n_blocks=2, out_dim=1, dropout=0.1, num_heads=1, num_head_channels=-1,
                  use_new_attention_order=False, use_checkpoint=False, use_fp16=False):
-        if out_dim != 1:
-            raise NotImplementedError("SigmaModel: out_dim must be 1")
-        self.dim, self.channels, self.n_blocks = dim, channels, n_blocks
         self.heads = _num_heads(num_heads, num_head_channels, channels)
         self.new_order = use_new_attention_order
-        super().__init__()
+        super().__init__(dim, channels, n_blocks, out_dim)
         if use_fp16:
             self.convert_to_fp16()
 
-    def _layout(self):
-        out, idx, d = [], 0, self.dim
-        for i in range(self.n_blocks):
-            pad = d % 2 != 0
-            if pad:
-                d += 1
-            idx += 1
-            res = f"down_layer.{idx}"; idx += 1
-            attn = None
-            if i == 0:
-                attn = f"down_layer.{idx}"; idx += 1
-            down = f"down_layer.{idx}"; idx += 1
-            d //= 2
-            out.append((pad, res, attn, down))
-        return out, d
+    def _spec_block(self, sb, p, c):
+        _spec_resblock(sb, p, c, c, 0, False, with_emb=False)
 
-    def param_spec(self):
-        sb = SpecBuilder()
-        c = self.channels
-        layout, d = self._layout()
-        for pad, res, attn, down in layout:
-            _spec_resblock(sb, res, c, c, 0, False, with_emb=False)
-            if attn:
-                _spec_attention(sb, attn, c)
-            sb.conv(down + ".op", c, c, 3)
-        sb.linear("fc_layer.1", 128, c * d * d)
-        sb.batchnorm("fc_layer.2", 128)
-        sb.linear("final_mlp", 1, 128)
-        return sb.spec
+    _spec_attention = staticmethod(_spec_attention)
 
-    def _build(self, sd, device, dtype):
-        P = type("Plan", (), {})()
-        layout, _ = self._layout()
-        P.blocks = []
-        for pad, res, attn, down in layout:
-            P.blocks.append((pad, _ResBlock(sd, res, dtype, device, None, False),
-                             _Attention(sd, attn, dtype, device, self.heads, self.new_order) if attn else None,
-                             pack(sd, down + ".op", dtype, device)))
-        P.head = SigmaHead(sd, device, ACT_GELU, allow_split=ops.is16(dtype))
-        return P
+    def _make_block(self, sd, p, dtype, device):
+        return _resblock(sd, p, dtype, device, None, False)
 
-    def run_nhwc(self, h: torch.Tensor) -> torch.Tensor:
-        """feat NHWC (compute dtype) -> r[b] f32."""
-        P = self.plan()
-        with torch.cuda.device(self.device):
-            for pad, res, attn, down in P.blocks:
-                if pad:
-                    h = ops.pad_rb(h)
-                h = res(h, None, None)
-                if attn is not None:
-                    h = attn(h)
-                h = ops.conv2d(h, down, stride=2, pad=(1, 1))
-            return P.head(h)
+    def _make_attention(self, sd, p, dtype, device):
+        return _attention(sd, p, dtype, device, self.heads, self.new_order)
 
-    def forward(self, feat):
-        """feat: NCHW f32 as the reference passes it -> (B,1,1,1) f32."""
-        self._require_gpu()
-        x = as_f32_cuda(feat, self.device)
-        h = ops.nchw_f32_to_nhwc(x, self.compute_dtype)
-        return self.run_nhwc(h).view(-1, 1, 1, 1)
+    def _downsample(self, h, pw):
+        return ops.conv2d(h, pw, stride=2, pad=(1, 1))

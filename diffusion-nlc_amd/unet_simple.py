@@ -12,13 +12,15 @@
 from __future__ import annotations
 
 import math
+from types import SimpleNamespace
 from typing import Optional
 
 import torch
 
 from . import ops
-from ._ext import ACT_GELU, ACT_NONE, ACT_SILU
-from .hipnet import EmbBank, HipModule, Norm, SigmaHead, SpecBuilder, as_f32_cuda, first_conv_weight, pack, pack_w
+from ._ext import ACT_SILU
+from .hipnet import (EmbBank, HipModule, Norm, ResBlock, SelfAttention, SigmaNet, SpecBuilder, first_conv_weight, pack, pack_opt, pack_w,
+                     qkv_row_scale)
 
 GN_GROUPS, GN_EPS = 32, 1e-6       # Normalize (src/unet_simple.py:32-33)
 
@@ -40,46 +42,20 @@ def _spec_attn(sb: SpecBuilder, p, c):
         sb.conv(f"{p}.{n}", c, c, 1)
 
 
-class _ResnetBlock:
-    def __init__(self, sd, p, dtype, device, bank: Optional[EmbBank]):
-        self.n1 = Norm(sd, p + ".norm1", device, GN_GROUPS, GN_EPS)
-        self.c1 = pack(sd, p + ".conv1", dtype, device)
-        self.n2 = Norm(sd, p + ".norm2", device, GN_GROUPS, GN_EPS)
-        self.c2 = pack(sd, p + ".conv2", dtype, device)
-        self.nin = pack(sd, p + ".nin_shortcut", dtype, device) if (p + ".nin_shortcut.weight") in sd else None
-        self.emb_off = bank.add(sd[p + ".temb_proj.weight"], sd[p + ".temb_proj.bias"])[0] if bank is not None else None
-
-    def __call__(self, x, x1, emb_all):
-        both = self.n1.with_skip(x, self.nin, silu=True, x1=x1) if self.nin is not None else None      # norm1 and nin_shortcut: one read
-        emb = None if self.emb_off is None else emb_all[:, self.emb_off:]
-        if both is not None:
-            hn, res = both
-            h = ops.conv2d(hn, self.c1, emb=emb)
-        else:                              # (small maps: the normalisation is applied by the convolution itself, hipnet.Norm.then_conv)
-            h, res = self.n1.then_conv(x, self.c1, silu=True, x1=x1, emb=emb), None
-        if res is None:
-            res = ops.conv2d(x, self.nin, x1=x1) if self.nin is not None else x
-        return self.n2.then_conv(h, self.c2, silu=True, res=res)
+def _resnet_block(sd, p, dtype, device, bank: Optional[EmbBank]) -> ResBlock:
+    norm = lambda q: Norm(sd, p + q, device, GN_GROUPS, GN_EPS)
+    return ResBlock(norm(".norm1"), pack(sd, p + ".conv1", dtype, device), norm(".norm2"), pack(sd, p + ".conv2", dtype, device),
+                    pack_opt(sd, p + ".nin_shortcut", dtype, device),
+                    None if bank is None else bank.add(sd[p + ".temb_proj.weight"], sd[p + ".temb_proj.bias"])[0])
 
 
-class _AttnBlock:
-    def __init__(self, sd, p, dtype, device):
-        c = sd[p + ".q.weight"].shape[0]
-        self.norm = Norm(sd, p + ".norm", device, GN_GROUPS, GN_EPS)
-        w = torch.cat([sd[f"{p}.{n}.weight"] for n in ("q", "k", "v")], 0)
-        b = torch.cat([sd[f"{p}.{n}.bias"] for n in ("q", "k", "v")], 0)
-        scale = torch.ones(3 * c, dtype=torch.float64)
-        scale[: 2 * c] = float(c) ** -0.25                  # w_ * c^-1/2 (:177) split evenly over q and k
-        f, self.base2 = ops.attention_logit_scale(dtype)
-        scale[:c] *= f
-        self.qkv = pack_w(w, b, dtype, device, row_scale=scale)
-        self.proj = pack(sd, p + ".proj_out", dtype, device)
-
-    def __call__(self, x):
-        B, H, W, C = x.shape
-        qkv = ops.conv2d(self.norm(x, silu=False), self.qkv)
-        a = ops.attention(qkv.view(B, H * W, 3 * C), 1, base2=self.base2)
-        return ops.conv2d(a.view(B, H, W, C), self.proj, res=x)
+def _attn_block(sd, p, dtype, device) -> SelfAttention:
+    c = sd[p + ".q.weight"].shape[0]
+    w = torch.cat([sd[f"{p}.{n}.weight"] for n in ("q", "k", "v")], 0)
+    b = torch.cat([sd[f"{p}.{n}.bias"] for n in ("q", "k", "v")], 0)
+    scale, base2 = qkv_row_scale(c, float(c) ** -0.25, dtype)                # w_ * c^-1/2 (:177) split evenly over q and k
+    return SelfAttention(Norm(sd, p + ".norm", device, GN_GROUPS, GN_EPS), pack_w(w, b, dtype, device, row_scale=scale),
+                         pack(sd, p + ".proj_out", dtype, device), 1, base2)
 
 
 class Model(HipModule):
@@ -165,7 +141,7 @@ class Model(HipModule):
         return sb.spec
 
     def _build(self, sd, device, dtype):
-        P = type("Plan", (), {})()
+        P = SimpleNamespace()
         down, mid_ch, up, last = self._layout()
         half = self.ch // 2
         k = math.log(10000) / (half - 1)                                   # src/unet_simple.py:16-18
@@ -174,12 +150,12 @@ class Model(HipModule):
         P.d1 = pack(sd, "temb.dense.1", torch.float32, device)
         P.conv_in = first_conv_weight(sd, "conv_in", device)
         bank = EmbBank()
-        mk = lambda p: _ResnetBlock(sd, p, dtype, device, bank)
-        P.down = [([(mk(p), _AttnBlock(sd, a, dtype, device) if a else None) for p, ci, co, a in blocks],
+        mk = lambda p: _resnet_block(sd, p, dtype, device, bank)
+        P.down = [([(mk(p), _attn_block(sd, a, dtype, device) if a else None) for p, ci, co, a in blocks],
                    (pack(sd, ds + ".conv", dtype, device) if self.resamp_with_conv else "pool") if ds else None)
                   for blocks, ds, cin in down]
-        P.mid1, P.mid_attn, P.mid2 = mk("mid.block_1"), _AttnBlock(sd, "mid.attn_1", dtype, device), mk("mid.block_2")
-        P.up = [([(mk(p), _AttnBlock(sd, a, dtype, device) if a else None) for p, ci, co, a in blocks],
+        P.mid1, P.mid_attn, P.mid2 = mk("mid.block_1"), _attn_block(sd, "mid.attn_1", dtype, device), mk("mid.block_2")
+        P.up = [([(mk(p), _attn_block(sd, a, dtype, device) if a else None) for p, ci, co, a in blocks],
                  (pack(sd, us + ".conv", dtype, device) if self.resamp_with_conv else "nearest") if us else None)
                 for lvl, blocks, us, cin in up]
         bank.finalize(device, allow_split=ops.is16(dtype))
@@ -232,14 +208,6 @@ class Model(HipModule):
                 return out
             return out, (feat if feat_nhwc else ops.nhwc_to_nchw_f32(feat))
 
-    def _prep(self, x, t):
-        self._require_gpu()
-        x = as_f32_cuda(x, self.device)
-        t = as_f32_cuda(t, self.device).reshape(-1)
-        if t.numel() == 1 and x.shape[0] > 1:
-            t = t.expand(x.shape[0]).contiguous()
-        return x, t
-
     def forward(self, x, t):
         return self.run(*self._prep(x, t), mode="forward")
 
@@ -250,66 +218,18 @@ class Model(HipModule):
         return self.run(*self._prep(x, t), mode="both")
 
 
-class SigmaModel(HipModule):
+class SigmaModel(SigmaNet):
     """src/unet_simple.py:481-517."""
 
     def __init__(self, dim=4, channels=64, n_blocks=2, out_dim=1, dropout=0.1):
-        if out_dim != 1:
-            raise NotImplementedError("SigmaModel: out_dim must be 1")
-        self.dim, self.channels, self.n_blocks = dim, channels, n_blocks
-        super().__init__()
+        super().__init__(dim, channels, n_blocks, out_dim)
 
-    def _layout(self):
-        out, idx, d = [], 0, self.dim
-        for i in range(self.n_blocks):
-            pad = d % 2 != 0
-            if pad:
-                d += 1
-            idx += 1
-            res = f"down_layer.{idx}"; idx += 1
-            attn = None
-            if i == 0:
-                attn = f"down_layer.{idx}"; idx += 1
-            down = f"down_layer.{idx}"; idx += 1
-            d //= 2
-            out.append((pad, res, attn, down))
-        return out, d
+    def _spec_block(self, sb, p, c):
+        _spec_resnet(sb, p, c, c, 0)
 
-    def param_spec(self):
-        sb = SpecBuilder()
-        c = self.channels
-        layout, d = self._layout()
-        for pad, res, attn, down in layout:
-            _spec_resnet(sb, res, c, c, 0)
-            if attn:
-                _spec_attn(sb, attn, c)
-            sb.conv(down + ".conv", c, c, 3)
-        sb.linear("fc_layer.1", 128, c * d * d)
-        sb.batchnorm("fc_layer.2", 128)
-        sb.linear("final_mlp", 1, 128)
-        return sb.spec
+    _spec_attention = staticmethod(_spec_attn)
 
-    def _build(self, sd, device, dtype):
-        P = type("Plan", (), {})()
-        layout, _ = self._layout()
-        P.blocks = [(pad, _ResnetBlock(sd, res, dtype, device, None), _AttnBlock(sd, attn, dtype, device) if attn else None,
-                     pack(sd, down + ".conv", dtype, device)) for pad, res, attn, down in layout]
-        P.head = SigmaHead(sd, device, ACT_GELU, allow_split=ops.is16(dtype))
-        return P
+    def _make_block(self, sd, p, dtype, device):
+        return _resnet_block(sd, p, dtype, device, None)
 
-    def run_nhwc(self, h):
-        P = self.plan()
-        with torch.cuda.device(self.device):
-            for pad, res, attn, down in P.blocks:
-                if pad:
-                    h = ops.pad_rb(h)
-                h = res(h, None, None)
-                if attn is not None:
-                    h = attn(h)
-                h = ops.conv2d(h, down, stride=2, pad=(0, 0), out_hw=(h.shape[1] // 2, h.shape[2] // 2))
-            return P.head(h)
-
-    def forward(self, feat):
-        self._require_gpu()
-        h = ops.nchw_f32_to_nhwc(as_f32_cuda(feat, self.device), self.compute_dtype)
-        return self.run_nhwc(h).view(-1, 1, 1, 1)
+    _make_attention = staticmethod(_attn_block)
