@@ -15,7 +15,7 @@ _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("NLC_HIP_LIB", _HERE / "libnlc_hip.so"))     # override: kernel A/B experiments only
 BUILD_SCRIPT = _HERE / "csrc" / "build.sh"
 
-ABI_VERSION = 9                 # NLC_ABI_VERSION of include/nlc_hip.h
+ABI_VERSION = 10                # NLC_ABI_VERSION of include/nlc_hip.h
 NLC_F32, NLC_BF16, NLC_F16 = 0, 1, 2
 MATH_NATIVE, MATH_F16X3 = 0, 1      # nlc_conv_desc.math / nlc_pack_conv_weights_ex
 ACT_NONE, ACT_SILU, ACT_GELU = 0, 1, 2
@@ -182,6 +182,9 @@ SIGNATURES = {
     "nlc_group_A": (C.c_int, [_vp, GroupDesc, _vp, _vp]),
     "nlc_group_Apinv": (C.c_int, [_vp, GroupDesc, _vp, _vp]),
     "nlc_group_project": (C.c_int, [_vp, _vp, GroupDesc, _vp]),
+    "nlc_gd_workspace_bytes": (C.c_int64, [_i, _i64]),
+    "nlc_group_gd": (C.c_int, [_vp, _vp, GroupDesc, _f, _i, _i, _vp, _vp]),
+    "nlc_inpaint_gd": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _vp, _vp]),
 }
 
 _lib = None

@@ -14,8 +14,12 @@ projection  x0 <- x0 - A^+(A x0 - y)).
   runs clip / ``nlc_group_project`` / x_prev (three launches; the projection needs a per-group reduction that the
   element-wise scheduler kernel does not have).
 
-The other degradations of the reference (bicubic SR, deblurring, compressed sensing, denoising), the ``*_gd`` /
-``simple`` projections and ``ddrm`` with the group-sum operators raise NotImplementedError.
+* ``svd_gd`` (``affine_proj_GD``, ``image_sample.py:344-357,384-399``) runs n_iter gradient steps on ||A x0 - y||_1 or _2 for
+  the same three operators.  Their A A^T is a multiple of the identity, so the gradient and the whole iteration have a closed
+  form: ``nlc_group_gd`` / ``nlc_inpaint_gd`` (``GradientProjection``), one launch for l1 and two for l2 whatever n_iter is.
+
+The other degradations of the reference (bicubic SR, deblurring, compressed sensing, denoising), the ``simple`` / ``simple_gd``
+projections and ``ddrm`` with the group-sum operators raise NotImplementedError.
 """
 from __future__ import annotations
 
@@ -79,6 +83,42 @@ class Inpainting:
         return out
 
     At = A_pinv          # singular values are all 1: A^T = A^+
+
+    @ops.on_device
+    def gd_(self, x0, known, lr, n_iter, loss, workspace=None):
+        """``n_iter`` steps of x0 <- x0 - lr grad ||A x0 - y||_p in place (``nlc_inpaint_gd``).  ``x0``: contiguous f32 (B, C, H, W)
+        on this device; ``known``: A^+ y in the same shape.  Only known entries move."""
+        if not (x0.is_contiguous() and x0.dtype == torch.float32 and x0.is_cuda and x0.device == known.device
+                and known.is_contiguous() and known.dtype == torch.float32):
+            raise NlcError("gd_: x0 and known must be contiguous float32 tensors on the operator's device")
+        B, C, HW = x0.shape[0], self.channels, self.img_dim ** 2
+        if x0.numel() != B * C * HW or known.numel() != x0.numel():
+            raise NlcError("gd_: shape mismatch")
+        loss = gd_loss_id(loss)
+        ws = workspace if workspace is not None else gd_workspace(B, C * HW, loss, x0.device)
+        check(_ext.load().nlc_inpaint_gd(x0.data_ptr(), self.mask_chw.data_ptr(), known.data_ptr(), B, C, HW, float(lr), int(n_iter),
+                                         loss, None if ws is None else ws.data_ptr(), _s()), "nlc_inpaint_gd")
+        return x0
+
+
+GD_LOSSES = {"l1": 1, "l2": 2}
+
+
+def gd_loss_id(loss):
+    """'l1' / 'l2' (or 1 / 2) -> the ``loss`` argument of nlc_group_gd / nlc_inpaint_gd."""
+    if loss in GD_LOSSES:
+        return GD_LOSSES[loss]
+    if loss in (1, 2):
+        return int(loss)
+    raise NlcError(f"constraint loss {loss!r}: expected 'l1' or 'l2'")
+
+
+def gd_workspace(B, entries_per_sample, loss, device):
+    """The l2 partial sums of one gradient-descent projection (``nlc_gd_workspace_bytes``); None for l1."""
+    if gd_loss_id(loss) != 2:
+        return None
+    n = _ext.load().nlc_gd_workspace_bytes(int(B), int(entries_per_sample))
+    return torch.empty(max(n, 8) // 8, dtype=torch.float64, device=device)
 
 
 def group_tables(weights):
@@ -168,6 +208,20 @@ class _GroupSum:
             raise NlcError("project_: shape mismatch")
         return group_project_(x0, y, self.desc(x0.shape[0]))
 
+    @ops.on_device
+    def gd_(self, x0, y, lr, n_iter, loss, workspace=None):
+        """``n_iter`` steps of x0 <- x0 - lr grad ||A x0 - y||_p in place (``nlc_group_gd``: one launch for l1, two for l2).
+        ``x0`` and ``y`` as for ``project_``."""
+        if not (x0.is_contiguous() and x0.dtype == torch.float32 and x0.device == y.device and x0.is_cuda):
+            raise NlcError("gd_: x0 must be a contiguous float32 tensor on the operator's device")
+        if x0.numel() != x0.shape[0] * self.channels * self.img_dim ** 2 or y.numel() != x0.shape[0] * self.groups:
+            raise NlcError("gd_: shape mismatch")
+        loss = gd_loss_id(loss)
+        ws = workspace if workspace is not None else gd_workspace(x0.shape[0], self.groups, loss, x0.device)
+        check(_ext.load().nlc_group_gd(x0.data_ptr(), y.data_ptr(), self.desc(x0.shape[0]), float(lr), int(n_iter), loss,
+                                       None if ws is None else ws.data_ptr(), _s()), "nlc_group_gd")
+        return x0
+
 
 class SuperResolution(_GroupSum):
     """functions/svd_operators.py:479-533: the mean of every ratio x ratio block; y is (B, C * (img_dim/ratio)^2), channel-major."""
@@ -248,15 +302,49 @@ class AffineGroup:
         return x0_t - Ap(A(x0_t.reshape(x0_t.size(0), -1)) - self.y).reshape(*x0_t.size())
 
 
-class Constraint_Function:
-    """image_sample.py:282-343 for deg='inpainting*' / 'sr_averagepooling' / 'colorization' and proj='svd'."""
+class GradientProjection:
+    """``partial(affine_proj_GD, infer_fn=Constraint.transform, loss_fn=..., n_iter=...)`` bound to y and lambda_t = lr
+    (image_sample.py:344-357,384-399): n_iter steps of x0 <- x0 - lr grad ||A x0 - y||_p, p = 1 ('l1') or 2 ('l2', per sample).
+    For these operators A A^T = s^2 I, so the steps collapse to a closed form (csrc/gd.h) and no autograd runs.  ``project_`` is
+    what the sampling loop calls, in place; calling the object runs the same kernels on a clone.  Holds no ``mask_chw`` / ``known``
+    attribute: the loop must not take it for the fused copy-the-known-pixels projection."""
 
-    def __init__(self, deg, A_funcs, channels=3, image_size=256, lr=1.0):
+    def __init__(self, op, y, shape, lr, n_iter, loss):
+        self.op, self.shape = op, tuple(shape)
+        self.lr, self.n_iter, self.loss = float(lr), int(n_iter), gd_loss_id(loss)
+        if isinstance(op, _GroupSum):
+            self._target = y.reshape(y.shape[0], -1).to(op.device, torch.float32).contiguous()
+            entries = op.groups
+        else:
+            self._target = op.A_pinv(y).view(*shape).contiguous()           # A^+ y: y on the known entries
+            entries = op.channels * op.img_dim ** 2
+        self._ws = gd_workspace(self.shape[0], entries, self.loss, self._target.device) if self._target.is_cuda else None
+
+    def project_(self, x0):
+        ws = self._ws if x0.shape[0] == self.shape[0] else None
+        return self.op.gd_(x0, self._target, self.lr, self.n_iter, self.loss, workspace=ws)
+
+    def __call__(self, x0_t):
+        x = x0_t.to(self._target.device, torch.float32).contiguous().clone()
+        return self.project_(x).view(*x0_t.size())
+
+
+PROJECTIONS = ("svd", "svd_gd")
+
+
+class Constraint_Function:
+    """image_sample.py:282-343 for deg='inpainting*' / 'sr_averagepooling' / 'colorization' and proj='svd' / 'svd_gd'."""
+
+    def __init__(self, deg, A_funcs, channels=3, image_size=256, lr=1.0, proj="svd", n_iter=10, loss="l1"):
         if "inp" not in deg and deg not in GROUP_SUM_CONSTRAINTS:
             raise NotImplementedError(deg)
+        if proj not in PROJECTIONS:
+            raise NotImplementedError(f"projection '{proj}': only {PROJECTIONS} are on the HIP path")
         self.deg, self.op = deg, A_funcs
         self.A, self.Ap = A_funcs.A, A_funcs.A_pinv
-        self.proj, self.channels, self.image_size, self.lr = "svd", channels, image_size, lr
+        self.proj, self.channels, self.image_size, self.lr = proj, channels, image_size, lr
+        self.n_iter, self.gd_loss = int(n_iter), loss
+        gd_loss_id(loss)
 
     def transform(self, x):
         return self.A(x)
@@ -270,12 +358,16 @@ class Constraint_Function:
         return Apy
 
     def constraint_fn(self, x0_t, y, lambda_t=None):
+        if self.proj == "svd_gd":                    # affine_proj_GD(x0_t, y, lambda_t, ...): lambda_t is the step size
+            return GradientProjection(self.op, y, x0_t.shape, self.lr if lambda_t is None else lambda_t, self.n_iter, self.gd_loss)(x0_t)
         if isinstance(self.op, _GroupSum):
             return AffineGroup(self.op, y, x0_t.shape)(x0_t)
         return AffineInpaint(self.op, y, x0_t.shape)(x0_t)
 
     def bind(self, y, shape):
         """The per-batch projection (what evaluate_constraint builds with functools.partial, image_sample.py:648)."""
+        if self.proj == "svd_gd":
+            return GradientProjection(self.op, y, shape, self.lr, self.n_iter, self.gd_loss)
         if isinstance(self.op, _GroupSum):
             return AffineGroup(self.op, y, shape)
         return AffineInpaint(self.op, y, shape)

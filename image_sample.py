@@ -13,9 +13,10 @@ diffusion-nlc_amd/.  Differences, all on side effects the reference hard-codes:
 * ``--synthetic NAME`` (extension): run without ``store/`` / ``results/`` files, with a built-in model
   configuration and the deterministic filler weights (the reference ships neither configs nor checkpoints).
 * ``--constraint``: the inpainting operators (``inpainting``, ``inpainting_half``), ``sr_averagepooling`` (block mean,
-  ``--constraint_scale`` = the ratio, 1..8) and ``colorization`` with ``--constraint_proj svd`` run on the HIP path
-  (SURVEY §8 f-1); the other SVD operators and the GD projections raise NotImplementedError, and so does
-  ``--constraint_proj ddrm`` with anything but inpainting.
+  ``--constraint_scale`` = the ratio, 1..8) and ``colorization`` with ``--constraint_proj svd`` or ``svd_gd`` (the
+  gradient-descent projection: ``--constraint_lr``, ``--constraint_iter``, ``--constraint_loss``) run on the HIP path
+  (SURVEY §8 f-1); the other SVD operators and the ``simple`` / ``simple_gd`` projections raise NotImplementedError, and so
+  does ``--constraint_proj ddrm`` with anything but inpainting.
   With ``--synthetic`` the validation images are seeded U(0,1) tensors and the mask is the seeded random 50 %
   of pixels of BASELINE config 4 (no dataset / ``store/inp_masks`` files ship with the reference).
 """
@@ -305,21 +306,23 @@ def projection_loop(self, *args, **kwargs):
 
 def get_constraint_function(args, image_size, channels):
     """image_sample.py:359-405 for the operators on the HIP path: inpainting with the 'svd' (or 'ddrm', same
-    operator) projection; average-pooling super-resolution and colorization with 'svd'."""
+    operator) projection; average-pooling super-resolution and colorization with 'svd'; all three with 'svd_gd'
+    (--constraint_lr / --constraint_iter / --constraint_loss: the step size, step count and norm of affine_proj_GD)."""
     from src.constraint_functions import GROUP_SUM_CONSTRAINTS, Constraint_Function, svd_constraint
     if args.constraint_proj == "ddrm" and args.constraint in GROUP_SUM_CONSTRAINTS:
         raise NotImplementedError(f"--constraint {args.constraint} --constraint_proj ddrm: the reference switches to the operators of "
                                   "functions/svd_replacement.py there, which have not been checked against the closed forms of "
                                   "the HIP path; use --constraint_proj svd")
     proj = "svd" if args.constraint_proj == "ddrm" else args.constraint_proj
-    if proj != "svd":
-        raise NotImplementedError(f"--constraint_proj {args.constraint_proj}: only 'svd' / 'ddrm' are on the HIP path")
+    if proj not in ("svd", "svd_gd"):
+        raise NotImplementedError(f"--constraint_proj {args.constraint_proj}: only 'svd' / 'ddrm' / 'svd_gd' are on the HIP path")
     name = args.constraint
     if args.synthetic and name == "inpainting":
         name = "inpainting_random"                 # seeded random 50 % mask instead of store/inp_masks/mask_random.pt
     op = svd_constraint(name, fn_scale=args.constraint_scale, device=args.device, base_mask_dir="store/inp_masks",
                         image_size=image_size, channels=channels)
-    return Constraint_Function(args.constraint, op, channels=channels, image_size=image_size, lr=args.constraint_lr)
+    return Constraint_Function(args.constraint, op, channels=channels, image_size=image_size, lr=args.constraint_lr, proj=proj,
+                               n_iter=getattr(args, "constraint_iter", 10), loss=getattr(args, "constraint_loss", "l1"))
 
 
 def synthetic_val_loader(args, shape, n_samples):

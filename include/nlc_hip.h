@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define NLC_ABI_VERSION 9
+#define NLC_ABI_VERSION 10
 
 enum { NLC_F32 = 0, NLC_BF16 = 1, NLC_F16 = 2 };
 /* matrix arithmetic of nlc_conv2d on NLC_F32 tensors (nlc_conv_desc.math; weights must be packed for the same mode):
@@ -542,6 +542,29 @@ typedef struct nlc_group_desc {
 int nlc_group_A(const float* x, nlc_group_desc desc, float* y_out, void* stream);
 int nlc_group_Apinv(const float* y, nlc_group_desc desc, float* x_out, void* stream);
 int nlc_group_project(float* x0, const float* y, nlc_group_desc desc, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Gradient-descent constraint projection (affine_proj_GD, image_sample.py:344-357; its set-up at :384-399) for the operators
+ * above, in place on the f32 [B][C][H][W] state:  n_iter steps of
+ *     X <- X - lr * grad_X sum_b ||A X_b - y_b||_p          loss = 1: p = 1 (l1) ; loss = 2: p = 2 (l2)
+ * The reference differentiates through A with autograd; for these operators A A^T = s2 I (s2 = sum_i w_i^2 of one group, 1 for
+ * inpainting), so with r = A x - y and c = lr * s2 the n_iter steps collapse (csrc/gd.h):
+ *   l1: the gradient is A^T sign(r), sign(0) = 0.  Per group  r^k = r^0 - c m_k,  m_k = sum_{j<k} sign(r^j),  and
+ *       x_i <- x_i - lr w_i m_n.  One launch, one read and one write of x0.
+ *   l2: the gradient is A^T r / ||r_b||_2 per sample b, 0 where the norm is 0.  rho_k = rho_0 - c M_k with rho_0 = ||r_b^0||_2,
+ *       M_k = sum_{j<k} sign(rho_j),  and  x_i <- x_i - lr w_i (r_g^0 / rho_0) M_n.  Two launches whatever n_iter is: per-workgroup
+ *       partial sums of r_g^2 (double) into `workspace`, then an apply pass that adds them in a fixed order.  No floating-point
+ *       atomics: the same input gives the same bits on every run.  A sample with rho_0 == 0 is left untouched.
+ *   nlc_group_gd   : desc as for nlc_group_project (same rules); desc.w serves A and A^T, desc.p is ignored.  y: [B][groups].
+ *   nlc_inpaint_gd : mask_chw f32 [C][HW], non-zero = known; known f32 [B][C][HW] = A^+ y.  Only known entries move.
+ *   nlc_gd_workspace_bytes(B, entries_per_sample): bytes of `workspace` for l2; entries_per_sample = groups per sample
+ *       (nlc_group_gd) or C*HW (nlc_inpaint_gd).  8-byte aligned; NULL is fine for l1.  0 for a non-positive argument.
+ * n_iter in 0..1024 (0: the identity, nothing is launched); lr finite (nlc_group_gd: lr * n_iter and lr * s2 finite in float too).
+ * ---------------------------------------------------------------------------------- */
+int64_t nlc_gd_workspace_bytes(int B, int64_t entries_per_sample);
+int nlc_group_gd(float* x0, const float* y, nlc_group_desc desc, float lr, int n_iter, int loss, void* workspace, void* stream);
+int nlc_inpaint_gd(float* x0, const float* mask_chw, const float* known, int B, int C, int HW, float lr, int n_iter, int loss,
+                   void* workspace, void* stream);
 
 #ifdef __cplusplus
 }
