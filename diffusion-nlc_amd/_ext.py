@@ -185,6 +185,8 @@ SIGNATURES = {
     "nlc_gd_workspace_bytes": (C.c_int64, [_i, _i64]),
     "nlc_group_gd": (C.c_int, [_vp, _vp, GroupDesc, _f, _i, _i, _vp, _vp]),
     "nlc_inpaint_gd": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _vp, _vp]),
+    "nlc_ssim3d_workspace_bytes": (C.c_int64, [_i, _i, _i, _i]),
+    "nlc_ssim3d": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -566,6 +566,28 @@ int nlc_group_gd(float* x0, const float* y, nlc_group_desc desc, float lr, int n
 int nlc_inpaint_gd(float* x0, const float* mask_chw, const float* known, int B, int C, int HW, float lr, int n_iter, int loss,
                    void* workspace, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * 3-D SSIM, the third number of a restoration run next to MSE and PSNR: ssim_fn (image_sample.py:571-582), which calls
+ * calculate_ssim with crop_border = 0, test_y_channel = False and its default ssim3d = True, i.e. _ssim_3d
+ * (basicsr/metrics/psnr_ssim.py:157-208, :251-337).  Per pair of [C][H][W] f32 images in [0, 1]:
+ *   a = round(sample * 255), b = round(orig * 255)   product rounded to f32, then to the nearest integer, ties to even; 0 .. 255
+ *   max_value = max(a) <= 1 ? 1 : 255 (over the sample alone) ;  C1 = (0.01 max_value)^2 ;  C2 = (0.03 max_value)^2
+ *   E[f] = f filtered over the volume (H, W, C) with the weights g_d g_h g_w, g = the normalised 11-tap Gaussian of sigma 1.5
+ *          (cv2.getGaussianKernel(11, 1.5)), replicate padding of 5 on every side of all three axes
+ *   out  = mean over H W C of (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2)),
+ *          mu1 = E[a], mu2 = E[b], s1 = E[a^2] - mu1^2, s2 = E[b^2] - mu2^2, s12 = E[ab] - mu1 mu2
+ * The reference runs five dense 1331-tap Conv3d per image; here the filter is applied separably in f32 (rows, columns, then the
+ * C x C matrix replicate padding makes of the channel axis), which differs from the dense form in rounding only (csrc/ssim.hip).
+ * One launch over all pairs and tiles, no filtered field in global memory, plus one small launch that adds each pair's tile sums
+ * (double) in a fixed order: no floating-point atomics, the same input gives the same bits on every run.
+ *   sample [N][C][H][W], orig [P][C][H][W]: pair n is (sample[n], orig[n % P]); 1 <= P <= N, N % P == 0 (per-step logs compare
+ *   many states with the same originals).  1 <= C <= 4; 1 <= H, W <= 65536; N >= 1.  Values outside [0, 1] are clamped after rounding.
+ *   out [N] double.  workspace: nlc_ssim3d_workspace_bytes bytes, 8-byte aligned, never NULL; the size is 0 for a shape the call rejects.
+ * ---------------------------------------------------------------------------------- */
+int64_t nlc_ssim3d_workspace_bytes(int N, int C, int H, int W);
+int nlc_ssim3d(const float* sample /*[N][C][H][W], [0,1]*/, const float* orig /*[P][C][H][W]*/, int N, int P,
+               int C, int H, int W, double* out /*[N]*/, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
