@@ -10,7 +10,8 @@ projection  x0 <- x0 - A^+(A x0 - y)).
   known), A and A^+ themselves are the two gather kernels of ``csrc/constraint.hip``.
 * Super-resolution and colorization are "one weighted sum per group of n entries" (an r x r block, or the 3 channels of
   a pixel).  With the weights w and p_i = w_i / sum w^2:  A(x)[g] = sum_i w_i x_i,  A^+(y)[i of g] = p_i y[g],  and the
-  projection is  x0_i + p_i (y[g] - sum_j w_j x0_j):  the three kernels of ``csrc/restore.hip``.  Per step the loop
+  projection is  x0_i + p_i (y[g] - sum_j w_j x0_j):  three operations of the one group kernel of ``csrc/restore.hip``
+  (layout x operation; the ``svd_gd`` phases below are the other three).  Per step the loop
   runs clip / ``nlc_group_project`` / x_prev (three launches; the projection needs a per-group reduction that the
   element-wise scheduler kernel does not have).
 
@@ -33,8 +34,16 @@ from . import _ext, ops
 from ._ext import NlcError, check
 
 
-def _s():
-    return torch.cuda.current_stream().cuda_stream
+def _in_place(what, x0, partner, n_x0, n_partner):
+    """The state a kernel updates in place and the tensor it is held to: contiguous float32, x0 on a GPU, both on one device, with
+    ``n_x0`` / ``n_partner`` elements."""
+    for t in (x0, partner):
+        if not (t.is_contiguous() and t.dtype == torch.float32):
+            raise NlcError(f"{what}: x0 and its measurement must be contiguous float32 tensors")
+    if not (x0.is_cuda and x0.device == partner.device):
+        raise NlcError(f"{what}: x0 and its measurement must be on the operator's device")
+    if x0.numel() != n_x0 or partner.numel() != n_partner:
+        raise NlcError(f"{what}: shape mismatch")
 
 
 class Inpainting:
@@ -66,7 +75,7 @@ class Inpainting:
         B, C, HW = x.shape
         nk = self.kept_indices.numel()
         out = torch.empty(B, nk, device=self.device, dtype=torch.float32)
-        check(_ext.load().nlc_inpaint_A(x.data_ptr(), self.kept_indices.data_ptr(), out.data_ptr(), B, C, HW, nk, _s()),
+        check(_ext.load().nlc_inpaint_A(x.data_ptr(), self.kept_indices.data_ptr(), out.data_ptr(), B, C, HW, nk, ops._stream()),
               "nlc_inpaint_A")
         return out
 
@@ -78,7 +87,7 @@ class Inpainting:
             raise ValueError("A_pinv: measurement length mismatch")
         C, HW = self.channels, self.img_dim ** 2
         out = torch.empty(B, C * HW, device=self.device, dtype=torch.float32)
-        check(_ext.load().nlc_inpaint_Apinv(y.data_ptr(), self._inv.data_ptr(), out.data_ptr(), B, C, HW, nk, _s()),
+        check(_ext.load().nlc_inpaint_Apinv(y.data_ptr(), self._inv.data_ptr(), out.data_ptr(), B, C, HW, nk, ops._stream()),
               "nlc_inpaint_Apinv")
         return out
 
@@ -88,16 +97,12 @@ class Inpainting:
     def gd_(self, x0, known, lr, n_iter, loss, workspace=None):
         """``n_iter`` steps of x0 <- x0 - lr grad ||A x0 - y||_p in place (``nlc_inpaint_gd``).  ``x0``: contiguous f32 (B, C, H, W)
         on this device; ``known``: A^+ y in the same shape.  Only known entries move."""
-        if not (x0.is_contiguous() and x0.dtype == torch.float32 and x0.is_cuda and x0.device == known.device
-                and known.is_contiguous() and known.dtype == torch.float32):
-            raise NlcError("gd_: x0 and known must be contiguous float32 tensors on the operator's device")
         B, C, HW = x0.shape[0], self.channels, self.img_dim ** 2
-        if x0.numel() != B * C * HW or known.numel() != x0.numel():
-            raise NlcError("gd_: shape mismatch")
+        _in_place("gd_", x0, known, B * C * HW, B * C * HW)
         loss = gd_loss_id(loss)
         ws = workspace if workspace is not None else gd_workspace(B, C * HW, loss, x0.device)
         check(_ext.load().nlc_inpaint_gd(x0.data_ptr(), self.mask_chw.data_ptr(), known.data_ptr(), B, C, HW, float(lr), int(n_iter),
-                                         loss, None if ws is None else ws.data_ptr(), _s()), "nlc_inpaint_gd")
+                                         loss, None if ws is None else ws.data_ptr(), ops._stream()), "nlc_inpaint_gd")
         return x0
 
 
@@ -144,20 +149,20 @@ def group_A(x, desc):
     B = desc.B
     n = (desc.C * (desc.H // max(desc.r, 1)) * (desc.W // max(desc.r, 1))) if desc.mode == _ext.GROUP_BLOCK else desc.H * desc.W
     out = torch.empty(B, n, device=x.device, dtype=torch.float32)
-    check(_ext.load().nlc_group_A(x.data_ptr(), desc, out.data_ptr(), _s()), "nlc_group_A")
+    check(_ext.load().nlc_group_A(x.data_ptr(), desc, out.data_ptr(), ops._stream()), "nlc_group_A")
     return out
 
 
 def group_Apinv(y, desc):
     """x = A^+ y (or A^T y with w in the place of p).  Returns (B, C*H*W)."""
     out = torch.empty(desc.B, desc.C * desc.H * desc.W, device=y.device, dtype=torch.float32)
-    check(_ext.load().nlc_group_Apinv(y.data_ptr(), desc, out.data_ptr(), _s()), "nlc_group_Apinv")
+    check(_ext.load().nlc_group_Apinv(y.data_ptr(), desc, out.data_ptr(), ops._stream()), "nlc_group_Apinv")
     return out
 
 
 def group_project_(x0, y, desc):
     """x0 <- x0 + p (y - A x0), in place, one launch."""
-    check(_ext.load().nlc_group_project(x0.data_ptr(), y.data_ptr(), desc, _s()), "nlc_group_project")
+    check(_ext.load().nlc_group_project(x0.data_ptr(), y.data_ptr(), desc, ops._stream()), "nlc_group_project")
     return x0
 
 
@@ -202,24 +207,18 @@ class _GroupSum:
     @ops.on_device
     def project_(self, x0, y):
         """x0 <- x0 - A^+(A x0 - y) in place.  ``x0``: contiguous f32 (B, C, H, W) on this device; ``y``: contiguous f32 (B, groups)."""
-        if not (x0.is_contiguous() and x0.dtype == torch.float32 and x0.device == y.device and x0.is_cuda):
-            raise NlcError("project_: x0 must be a contiguous float32 tensor on the operator's device")
-        if x0.numel() != x0.shape[0] * self.channels * self.img_dim ** 2 or y.numel() != x0.shape[0] * self.groups:
-            raise NlcError("project_: shape mismatch")
+        _in_place("project_", x0, y, x0.shape[0] * self.channels * self.img_dim ** 2, x0.shape[0] * self.groups)
         return group_project_(x0, y, self.desc(x0.shape[0]))
 
     @ops.on_device
     def gd_(self, x0, y, lr, n_iter, loss, workspace=None):
         """``n_iter`` steps of x0 <- x0 - lr grad ||A x0 - y||_p in place (``nlc_group_gd``: one launch for l1, two for l2).
         ``x0`` and ``y`` as for ``project_``."""
-        if not (x0.is_contiguous() and x0.dtype == torch.float32 and x0.device == y.device and x0.is_cuda):
-            raise NlcError("gd_: x0 must be a contiguous float32 tensor on the operator's device")
-        if x0.numel() != x0.shape[0] * self.channels * self.img_dim ** 2 or y.numel() != x0.shape[0] * self.groups:
-            raise NlcError("gd_: shape mismatch")
+        _in_place("gd_", x0, y, x0.shape[0] * self.channels * self.img_dim ** 2, x0.shape[0] * self.groups)
         loss = gd_loss_id(loss)
         ws = workspace if workspace is not None else gd_workspace(x0.shape[0], self.groups, loss, x0.device)
         check(_ext.load().nlc_group_gd(x0.data_ptr(), y.data_ptr(), self.desc(x0.shape[0]), float(lr), int(n_iter), loss,
-                                       None if ws is None else ws.data_ptr(), _s()), "nlc_group_gd")
+                                       None if ws is None else ws.data_ptr(), ops._stream()), "nlc_group_gd")
         return x0
 
 
@@ -358,16 +357,13 @@ class Constraint_Function:
         return Apy
 
     def constraint_fn(self, x0_t, y, lambda_t=None):
-        if self.proj == "svd_gd":                    # affine_proj_GD(x0_t, y, lambda_t, ...): lambda_t is the step size
-            return GradientProjection(self.op, y, x0_t.shape, self.lr if lambda_t is None else lambda_t, self.n_iter, self.gd_loss)(x0_t)
-        if isinstance(self.op, _GroupSum):
-            return AffineGroup(self.op, y, x0_t.shape)(x0_t)
-        return AffineInpaint(self.op, y, x0_t.shape)(x0_t)
+        return self.bind(y, x0_t.shape, lambda_t)(x0_t)
 
-    def bind(self, y, shape):
-        """The per-batch projection (what evaluate_constraint builds with functools.partial, image_sample.py:648)."""
+    def bind(self, y, shape, lr=None):
+        """The per-batch projection (what evaluate_constraint builds with functools.partial, image_sample.py:648).  ``lr``: the
+        step size of svd_gd in the place of ``self.lr`` (affine_proj_GD(x0_t, y, lambda_t, ...): lambda_t is the step size)."""
         if self.proj == "svd_gd":
-            return GradientProjection(self.op, y, shape, self.lr, self.n_iter, self.gd_loss)
+            return GradientProjection(self.op, y, shape, self.lr if lr is None else lr, self.n_iter, self.gd_loss)
         if isinstance(self.op, _GroupSum):
             return AffineGroup(self.op, y, shape)
         return AffineInpaint(self.op, y, shape)

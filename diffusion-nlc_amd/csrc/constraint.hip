@@ -6,7 +6,7 @@
 // The per-step projection  x0 <- x0 - A^+(A x0 - y)  ("copy the known pixels") is fused into
 // nlc_sched_step (mask / known), so these two kernels run once per batch.
 // nlc_inpaint_gd is the gradient-descent projection (affine_proj_GD, image_sample.py:344-357,384-399) over the same mask / known
-// pair; its closed forms are in gd.h.
+// pair.  Its closed forms, the phases of a pass and their launch order are in gd.h; this file says what one item of a pass is.
 #include "common.h"
 #include "gd.h"
 
@@ -34,25 +34,15 @@ __global__ void inpaint_Apinv_kernel(const float* __restrict__ y, const int32_t*
     }
 }
 
-// Gradient-descent projection (gd.h) with A = "keep the known entries": s2 = 1, the residual of a known entry is x - known, a
-// missing entry has none and never moves.  x: [B][n], mask / known: [n] / [B][n], n = C*HW.  V = 4: float4 items (n % 4 == 0 and
-// all three bases 16-byte aligned), V = 1: scalar.
+// Gradient-descent projection with A = "keep the known entries": s2 = 1, the residual of a known entry is x - known, a missing
+// entry has none and never moves.  x: [B][n], mask / known: [n] / [B][n], n = C*HW.  An item of the pass (gd_pass, gd.h) is V
+// entries: V = 4: float4 items (n % 4 == 0 and all three bases 16-byte aligned), V = 1: scalar.
 template <int V, int PH>
 __global__ __launch_bounds__(NT) void inpaint_gd_kernel(float* x, const float* __restrict__ mask, const float* __restrict__ known,
                                                         int64_t n, const gd_params g) {
-    __shared__ double sh[NT / 64];
-    const int b = blockIdx.y;
-    float* xb = x + (int64_t)b * n;
-    const float* kb = known + (int64_t)b * n;
-    double* parts = g.partials + (int64_t)b * gridDim.x;
-    float q = 0.f;
-    if constexpr (PH == GD_L2_APPLY) {
-        q = gd_l2_scale(parts, gridDim.x, g, sh);
-        if (q == 0.f) return;
-    }
-    double acc = 0.0;
-    const int64_t items = n / V;
-    for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < items; i += (int64_t)gridDim.x * NT) {
+    float* xb = x + (int64_t)blockIdx.y * n;
+    const float* kb = known + (int64_t)blockIdx.y * n;
+    gd_pass<PH>(n / V, g, [&](int64_t i, float q, double& acc) __attribute__((always_inline)) {
         float v[V], m[V], k[V];
         if constexpr (V == 4) {
             const float4 tv = reinterpret_cast<const float4*>(xb)[i], tm = reinterpret_cast<const float4*>(mask)[i],
@@ -74,19 +64,7 @@ __global__ __launch_bounds__(NT) void inpaint_gd_kernel(float* x, const float* _
             if constexpr (V == 4) reinterpret_cast<float4*>(xb)[i] = make_float4(v[0], v[1], v[2], v[3]);
             else xb[i] = v[0];
         }
-    }
-    if constexpr (PH == GD_L2_SUM) {
-        acc = gd_block_sum(acc, sh);
-        if (threadIdx.x == 0) parts[blockIdx.x] = acc;
-    }
-}
-
-template <int PH>
-void launch_inpaint_gd(float* x, const float* mask, const float* known, int B, int64_t n, const gd_params& g, hipStream_t s) {
-    const bool vec = n % 4 == 0 && (((uintptr_t)x | (uintptr_t)mask | (uintptr_t)known) % 16) == 0;
-    const dim3 grid(gd_grid(vec ? n / 4 : n), B);
-    if (vec) hipLaunchKernelGGL((inpaint_gd_kernel<4, PH>), grid, dim3(NT), 0, s, x, mask, known, n, g);
-    else hipLaunchKernelGGL((inpaint_gd_kernel<1, PH>), grid, dim3(NT), 0, s, x, mask, known, n, g);
+    });
 }
 }  // namespace
 
@@ -100,16 +78,12 @@ extern "C" int nlc_inpaint_gd(float* x0, const float* mask_chw, const float* kno
     if (n_iter == 0) return NLC_OK;
     const gd_params g{lr, lr, (double)lr, n_iter, (double*)workspace};
     const int64_t n = (int64_t)C * HW;
-    hipStream_t s = (hipStream_t)stream;
-    if (loss == 1) {
-        launch_inpaint_gd<GD_L1>(x0, mask_chw, known, B, n, g, s);
-    } else {
-        launch_inpaint_gd<GD_L2_SUM>(x0, mask_chw, known, B, n, g, s);
-        NLC_CHECK_LAUNCH(name);
-        launch_inpaint_gd<GD_L2_APPLY>(x0, mask_chw, known, B, n, g, s);
-    }
-    NLC_CHECK_LAUNCH(name);
-    return NLC_OK;
+    const bool vec = n % 4 == 0 && (((uintptr_t)x0 | (uintptr_t)mask_chw | (uintptr_t)known) % 16) == 0;
+    const dim3 grid(gd_grid(vec ? n / 4 : n), B);
+    return gd_run(name, loss, [&](auto ph) {
+        if (vec) hipLaunchKernelGGL((inpaint_gd_kernel<4, ph()>), grid, dim3(NT), 0, (hipStream_t)stream, x0, mask_chw, known, n, g);
+        else hipLaunchKernelGGL((inpaint_gd_kernel<1, ph()>), grid, dim3(NT), 0, (hipStream_t)stream, x0, mask_chw, known, n, g);
+    });
 }
 
 extern "C" int nlc_inpaint_A(const float* x, const int64_t* kept, float* out, int B, int C, int64_t HW, int64_t nk, void* stream) {

@@ -11,9 +11,13 @@
 // up over the iterations.  l1 is local to a group: one launch, one read and one write of x0.  l2 is one per-sample reduction
 // (workgroup partials of sum r_g^2, in double, added in a fixed order: no floating-point atomics, bit-reproducible) plus one
 // apply pass, whatever n_iter is.
+// The structure of those passes stands here once: gd_pass is the device side (one sample per blockIdx.y, a grid-stride walk over
+// its items, the l2 partials and scale around it), gd_run the host side (which phases are launched, in which order).  An entry
+// point supplies what one item is - a group of restore.hip, a masked float4 / scalar of constraint.hip - and how a phase is launched.
 #pragma once
 #include "common.h"
 #include <cmath>
+#include <type_traits>
 
 enum { GD_L1 = 0, GD_L2_SUM = 1, GD_L2_APPLY = 2 };
 constexpr int GD_NT = 256;            // threads per workgroup of every GD kernel
@@ -79,4 +83,39 @@ __device__ __forceinline__ float gd_l2_scale(const double* parts, int nparts, co
         rho = fma(-g.c64, m, rho0);
     }
     return (float)((double)g.lr * m / rho0);
+}
+
+// One phase over the `items` of sample blockIdx.y, gridDim.x workgroups of GD_NT threads striding over them.  body(i, q, acc) does
+// item i: GD_L1 and GD_L2_APPLY update it (q: gd_l2_scale of this sample, l2 only), GD_L2_SUM adds its squared residuals to the
+// thread's `acc`, in double, in the order the thread meets them; the workgroup's total becomes its partial.  A lambda given as
+// body carries __attribute__((always_inline)): it is then inlined before it is optimised on its own, and the kernel compiles
+// to what the loop written out in place compiles to (otherwise the float4 loads of constraint.hip come out split).
+template <int PH, class Body> __device__ __forceinline__ void gd_pass(int64_t items, const gd_params& g, Body body) {
+    __shared__ double sh[GD_NT / 64];
+    double* parts = g.partials + (int64_t)blockIdx.y * gridDim.x;
+    float q = 0.f;
+    if constexpr (PH == GD_L2_APPLY) {
+        q = gd_l2_scale(parts, gridDim.x, g, sh);
+        if (q == 0.f) return;                          // rho_0 = 0 or M_n = 0: the sample stays as it is
+    }
+    double acc = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * GD_NT + threadIdx.x; i < items; i += (int64_t)gridDim.x * GD_NT) body(i, q, acc);
+    if constexpr (PH == GD_L2_SUM) {
+        acc = gd_block_sum(acc, sh);
+        if (threadIdx.x == 0) parts[blockIdx.x] = acc;
+    }
+}
+
+// The launches of one projection: l1 is one pass; l2 is the pass that sums, then the pass that applies.  launch(phase) enqueues
+// the kernel of one phase, given as std::integral_constant.  Sets the error itself.
+template <class Launch> int gd_run(const char* name, int loss, Launch launch) {
+    if (loss == 1) {
+        launch(std::integral_constant<int, GD_L1>{});
+    } else {
+        launch(std::integral_constant<int, GD_L2_SUM>{});
+        NLC_CHECK_LAUNCH(name);
+        launch(std::integral_constant<int, GD_L2_APPLY>{});
+    }
+    NLC_CHECK_LAUNCH(name);
+    return NLC_OK;
 }

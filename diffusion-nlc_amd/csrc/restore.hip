@@ -5,47 +5,99 @@
 //   A(x)[group]        = sum_i w_i x_i
 //   A^+(y)[i of group] = p_i y[group]
 //   x0 - A^+(A x0 - y) = x0_i + p_i (y[group] - sum_j w_j x0_j)            (affine_svd, image_sample.py:376-380)
-// BLOCK mode: a group is an r x r spatial block of one channel, i runs row-major inside the block, y is [b][c][by][bx]
-// (SuperResolution.Vt, :515).  CHANNEL mode: a group is the 3 channels of one pixel, y is [b][p].
-// One thread per group; the sum runs i = 0 .. n-1 as separately rounded products and additions, the update of the projection is
-// one fused multiply-add.  Bandwidth-bound: no LDS, no MFMA.  Adjacent threads take adjacent blocks of one block-row, so a
-// wavefront's row loads are contiguous; with r = 2 / 4 / 8 and a 16-byte aligned tensor a row is one float2 / float4 / two float4.
-// nlc_group_gd (affine_proj_GD, image_sample.py:344-357,384-399) walks the groups the same way; its closed forms are in gd.h.
+// and the gradient-descent projection nlc_group_gd (affine_proj_GD, image_sample.py:344-357,384-399; closed forms in gd.h).
+// The file is layout x operation.  A LAYOUT is the only code that knows where a group's entries live: BlockLayout<R, VEC> (an
+// r x r spatial block of one channel, i row-major inside the block, y is [b][c][by][bx]: SuperResolution.Vt, :515) and
+// ChannelLayout (the 3 channels of one pixel, y is [b][p]).  An OPERATION is what is done to the n entries v of one group and
+// its measurement: OpA, OpApinv, OpProject, OpGd<phase>.  group_kernel<Layout, Op> is the one kernel, with_layout the one place
+// that picks a layout; 12 layouts x 6 operations = 72 instantiations.
+// One thread per group; the sum runs i = 0 .. n-1 as separately rounded products and additions, every update is one fused
+// multiply-add.  Bandwidth-bound: no LDS, no MFMA.  Adjacent threads take adjacent blocks of one block-row, so a wavefront's row
+// loads are contiguous; with r = 2 / 4 / 8 and a 16-byte aligned tensor a row is one float2 / float4 / two float4.
 #include "common.h"
 #include "gd.h"
+#include <algorithm>
 
 namespace {
 constexpr int NT = 256;
-enum { OP_A = 0, OP_APINV = 1, OP_PROJECT = 2 };
+static_assert(NT == GD_NT, "the GD helpers reduce over GD_NT threads");
 
-template <int R, bool VEC> __device__ __forceinline__ void load_row(const float* p, float* v) {
-    if constexpr (VEC && R == 2) {
-        const float2 t = *reinterpret_cast<const float2*>(p);
-        v[0] = t.x; v[1] = t.y;
-    } else if constexpr (VEC && (R == 4 || R == 8)) {
+// ---- layouts: groups(d) per sample, and load / store of the N entries of group g of sample blockIdx.y --------------------------
+template <int R, bool VEC> struct BlockLayout {                  // x: [B][C][H][W] ; y: [B][C][H/R][W/R]
+    static constexpr int N = R * R;
+    static __host__ __device__ int64_t groups(const nlc_group_desc& d) { return (int64_t)d.C * (d.H / R) * (d.W / R); }
+
+    float* xb;
+    int W, Wb;
+    __device__ BlockLayout(float* x, const nlc_group_desc& d) : xb(x + (int64_t)blockIdx.y * d.C * d.H * d.W), W(d.W), Wb(d.W / R) {}
+
+    __device__ __forceinline__ float* corner(int64_t g) const {
+        if constexpr (R == 1) return xb + g;                     // the blocks are the entries: no division left to the optimiser
+        const int64_t row = g / Wb;                              // c * (H/R) + by: the block-row, counted over all channels
+        const int bx = (int)(g - row * Wb);
+        return xb + row * R * W + (int64_t)bx * R;
+    }
+    __device__ __forceinline__ void load(int64_t g, float* v) const {
+        const float* base = corner(g);
 #pragma unroll
-        for (int k = 0; k < R; k += 4) {
-            const float4 t = *reinterpret_cast<const float4*>(p + k);
-            v[k] = t.x; v[k + 1] = t.y; v[k + 2] = t.z; v[k + 3] = t.w;
+        for (int j = 0; j < R; ++j) load_row(base + (int64_t)j * W, v + j * R);
+    }
+    __device__ __forceinline__ void store(int64_t g, const float* v) const {
+        float* base = corner(g);
+#pragma unroll
+        for (int j = 0; j < R; ++j) store_row(base + (int64_t)j * W, v + j * R);
+    }
+
+    static __device__ __forceinline__ void load_row(const float* p, float* v) {
+        if constexpr (VEC && R == 2) {
+            const float2 t = *reinterpret_cast<const float2*>(p);
+            v[0] = t.x; v[1] = t.y;
+        } else if constexpr (VEC && (R == 4 || R == 8)) {
+#pragma unroll
+            for (int k = 0; k < R; k += 4) {
+                const float4 t = *reinterpret_cast<const float4*>(p + k);
+                v[k] = t.x; v[k + 1] = t.y; v[k + 2] = t.z; v[k + 3] = t.w;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < R; ++k) v[k] = p[k];
         }
-    } else {
-#pragma unroll
-        for (int k = 0; k < R; ++k) v[k] = p[k];
     }
-}
-
-template <int R, bool VEC> __device__ __forceinline__ void store_row(float* p, const float* v) {
-    if constexpr (VEC && R == 2) {
-        *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
-    } else if constexpr (VEC && (R == 4 || R == 8)) {
+    static __device__ __forceinline__ void store_row(float* p, const float* v) {
+        if constexpr (VEC && R == 2) {
+            *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
+        } else if constexpr (VEC && (R == 4 || R == 8)) {
 #pragma unroll
-        for (int k = 0; k < R; k += 4) *reinterpret_cast<float4*>(p + k) = make_float4(v[k], v[k + 1], v[k + 2], v[k + 3]);
-    } else {
+            for (int k = 0; k < R; k += 4) *reinterpret_cast<float4*>(p + k) = make_float4(v[k], v[k + 1], v[k + 2], v[k + 3]);
+        } else {
 #pragma unroll
-        for (int k = 0; k < R; ++k) p[k] = v[k];
+            for (int k = 0; k < R; ++k) p[k] = v[k];
+        }
     }
-}
+};
 
+struct ChannelLayout {                                           // x: [B][3][HW] ; y: [B][HW]
+    static constexpr int N = 3;
+    static __host__ __device__ int64_t groups(const nlc_group_desc& d) { return (int64_t)d.H * d.W; }
+
+    float* xb;
+    int64_t HW;
+    __device__ ChannelLayout(float* x, const nlc_group_desc& d) : xb(x + (int64_t)blockIdx.y * 3 * groups(d)), HW(groups(d)) {}
+
+    __device__ __forceinline__ void load(int64_t g, float* v) const {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = xb[c * HW + g];
+    }
+    __device__ __forceinline__ void store(int64_t g, const float* v) const {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) xb[c * HW + g] = v[c];
+    }
+};
+
+// ---- operations: op.apply<N>(v, yg, d, q, acc) on the N entries v of one group and its measurement yg.  Each says whether it
+//      reads x (v is loaded first), writes x (v is stored after) and writes y (yg is its result, not its input); `phase` is the
+//      gd_pass phase the groups are walked in, PLAIN for a grid-stride loop and nothing else; q / acc are that pass's. ------------
+constexpr int PLAIN = -1;
 // sum_i w_i v_i, i ascending: n products and n-1 additions, each rounded once (no contraction)
 template <int N> __device__ __forceinline__ float group_sum(const float* w, const float* v) {
     float s = __fmul_rn(w[0], v[0]);
@@ -54,83 +106,102 @@ template <int N> __device__ __forceinline__ float group_sum(const float* w, cons
     return s;
 }
 
-// x: [B][C][H][W] (read by OP_A, written by OP_APINV, both by OP_PROJECT) ; y: [B][C][H/R][W/R] (written by OP_A, read otherwise)
-template <int R, bool VEC, int OP>
-__global__ __launch_bounds__(NT) void group_block_kernel(float* x, float* y, const nlc_group_desc d) {
-    const int Wb = d.W / R;
-    const int64_t G = (int64_t)d.C * (d.H / R) * Wb;             // groups per sample
-    const int b = blockIdx.y;
-    float* xb = x + (int64_t)b * d.C * d.H * d.W;
-    float* yb = y + (int64_t)b * G;
-    for (int64_t g = (int64_t)blockIdx.x * NT + threadIdx.x; g < G; g += (int64_t)gridDim.x * NT) {
-        const int64_t row = g / Wb;                              // c * (H/R) + by: the block-row, counted over all channels
-        const int bx = (int)(g - row * Wb);
-        float* base = xb + row * R * d.W + (int64_t)bx * R;
-        float v[R * R];
-        if constexpr (OP == OP_APINV) {
-            const float yg = yb[g];
+struct OpA {
+    static constexpr bool reads_x = true, writes_x = false, writes_y = true;
+    static constexpr int phase = PLAIN;
+    template <int N> __device__ __forceinline__ void apply(float* v, float& yg, const nlc_group_desc& d, float, double&) const {
+        yg = group_sum<N>(d.w, v);
+    }
+};
+
+struct OpApinv {
+    static constexpr bool reads_x = false, writes_x = true, writes_y = false;
+    static constexpr int phase = PLAIN;
+    template <int N> __device__ __forceinline__ void apply(float* v, float& yg, const nlc_group_desc& d, float, double&) const {
 #pragma unroll
-            for (int i = 0; i < R * R; ++i) v[i] = __fmul_rn(d.p[i], yg);
+        for (int i = 0; i < N; ++i) v[i] = __fmul_rn(d.p[i], yg);
+    }
+};
+
+struct OpProject {
+    static constexpr bool reads_x = true, writes_x = true, writes_y = false;
+    static constexpr int phase = PLAIN;
+    template <int N> __device__ __forceinline__ void apply(float* v, float& yg, const nlc_group_desc& d, float, double&) const {
+        const float r = __fsub_rn(yg, group_sum<N>(d.w, v));
+#pragma unroll
+        for (int i = 0; i < N; ++i) v[i] = __fmaf_rn(d.p[i], r, v[i]);
+    }
+};
+
+// gradient-descent projection (gd.h): GD_L2_SUM adds r^2 to acc and leaves v alone; GD_L1 / GD_L2_APPLY do
+// x_i <- x_i - w_i a,  a = lr m_n (l1) or q r_g (l2), rounded once
+template <int PH> struct OpGd {
+    static constexpr bool reads_x = true, writes_x = PH != GD_L2_SUM, writes_y = false;
+    static constexpr int phase = PH;
+    gd_params g;
+    template <int N> __device__ __forceinline__ void apply(float* v, float& yg, const nlc_group_desc& d, float q, double& acc) const {
+        const float r = __fsub_rn(group_sum<N>(d.w, v), yg);
+        if constexpr (PH == GD_L2_SUM) {
+            acc += (double)r * (double)r;
         } else {
+            const float a = PH == GD_L1 ? __fmul_rn(g.lr, gd_l1_steps(r, g.c, g.n_iter)) : __fmul_rn(q, r);
 #pragma unroll
-            for (int j = 0; j < R; ++j) load_row<R, VEC>(base + (int64_t)j * d.W, v + j * R);
-            const float s = group_sum<R * R>(d.w, v);
-            if constexpr (OP == OP_A) {
-                yb[g] = s;
-            } else {
-                const float r = __fsub_rn(yb[g], s);
-#pragma unroll
-                for (int i = 0; i < R * R; ++i) v[i] = __fmaf_rn(d.p[i], r, v[i]);
-            }
+            for (int i = 0; i < N; ++i) v[i] = __fmaf_rn(-d.w[i], a, v[i]);
         }
-        if constexpr (OP != OP_A) {
-#pragma unroll
-            for (int j = 0; j < R; ++j) store_row<R, VEC>(base + (int64_t)j * d.W, v + j * R);
-        }
+    }
+};
+
+template <class L, class Op> __global__ __launch_bounds__(NT) void group_kernel(float* x, float* y, const nlc_group_desc d, const Op op) {
+    const L lay(x, d);
+    const int64_t G = L::groups(d);
+    float* yb = y + (int64_t)blockIdx.y * G;
+    auto group = [&](int64_t g, float q, double& acc) __attribute__((always_inline)) {
+        float v[L::N];
+        float yg = 0.f;
+        if constexpr (Op::reads_x) lay.load(g, v);
+        if constexpr (!Op::writes_y) yg = yb[g];
+        op.template apply<L::N>(v, yg, d, q, acc);
+        if constexpr (Op::writes_y) yb[g] = yg;
+        if constexpr (Op::writes_x) lay.store(g, v);
+    };
+    if constexpr (Op::phase == PLAIN) {
+        double unused = 0.0;
+        for (int64_t g = (int64_t)blockIdx.x * NT + threadIdx.x; g < G; g += (int64_t)gridDim.x * NT) group(g, 0.f, unused);
+    } else {
+        gd_pass<Op::phase>(G, op.g, group);
     }
 }
 
-// x: [B][3][HW] ; y: [B][HW]
-template <int OP>
-__global__ __launch_bounds__(NT) void group_channel_kernel(float* x, float* y, const nlc_group_desc d) {
-    const int64_t HW = (int64_t)d.H * d.W;
-    const int b = blockIdx.y;
-    float* xb = x + (int64_t)b * 3 * HW;
-    float* yb = y + (int64_t)b * HW;
-    for (int64_t p = (int64_t)blockIdx.x * NT + threadIdx.x; p < HW; p += (int64_t)gridDim.x * NT) {
-        float v[3];
-        if constexpr (OP == OP_APINV) {
-            const float yg = yb[p];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) v[c] = __fmul_rn(d.p[c], yg);
-        } else {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) v[c] = xb[c * HW + p];
-            const float s = group_sum<3>(d.w, v);
-            if constexpr (OP == OP_A) {
-                yb[p] = s;
-            } else {
-                const float r = __fsub_rn(yb[p], s);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) v[c] = __fmaf_rn(d.p[c], r, v[c]);
-            }
-        }
-        if constexpr (OP != OP_A) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) xb[c * HW + p] = v[c];
-        }
+// (mode, r, alignment of x) -> layout: f(std::type_identity<Layout>).  A row of R floats starts at a multiple of R floats from
+// the tensor's base (W % R == 0), so with R = 2 / 4 / 8 it is aligned for a vector access iff the base is, to 8 / 16 / 16 bytes.
+template <class F> void with_layout(const nlc_group_desc& d, const float* x, F f) {
+    if (d.mode == NLC_GROUP_CHANNEL) return f(std::type_identity<ChannelLayout>{});
+    auto block = [&](auto r) {
+        constexpr int R = r();
+        constexpr bool kCanVec = R == 2 || R == 4 || R == 8;
+        if (kCanVec && ((uintptr_t)x % (R == 2 ? 8 : 16)) == 0) f(std::type_identity<BlockLayout<R, kCanVec>>{});
+        else f(std::type_identity<BlockLayout<R, false>>{});
+    };
+    switch (d.r) {
+        case 1: block(std::integral_constant<int, 1>{}); break;
+        case 2: block(std::integral_constant<int, 2>{}); break;
+        case 3: block(std::integral_constant<int, 3>{}); break;
+        case 4: block(std::integral_constant<int, 4>{}); break;
+        case 5: block(std::integral_constant<int, 5>{}); break;
+        case 6: block(std::integral_constant<int, 6>{}); break;
+        case 7: block(std::integral_constant<int, 7>{}); break;
+        default: block(std::integral_constant<int, 8>{}); break;
     }
 }
 
-template <int R, int OP>
-void launch_block(float* x, float* y, const nlc_group_desc& d, dim3 grid, hipStream_t s) {
-    // a row of R floats starts at a multiple of R floats from the tensor's base (W % R == 0): aligned iff the base is
-    constexpr bool kCanVec = R == 2 || R == 4 || R == 8;
-    const uintptr_t align = R == 2 ? 8 : 16;
-    if (kCanVec && ((uintptr_t)x % align) == 0)
-        hipLaunchKernelGGL((group_block_kernel<R, kCanVec, OP>), grid, dim3(NT), 0, s, x, y, d);
-    else
-        hipLaunchKernelGGL((group_block_kernel<R, false, OP>), grid, dim3(NT), 0, s, x, y, d);
+// a checked descriptor; the workgroups per sample are gd_grid for a GD phase (the partials, nlc_gd_workspace_bytes) and at most
+// 1024 otherwise
+template <class Op> void launch_group(float* x, float* y, const nlc_group_desc& d, const Op& op, void* stream) {
+    with_layout(d, x, [&](auto layout) {
+        using L = typename decltype(layout)::type;
+        const int g = Op::phase == PLAIN ? std::min(cdiv(L::groups(d), NT), 1024) : gd_grid(L::groups(d));
+        hipLaunchKernelGGL((group_kernel<L, Op>), dim3(g, d.B), dim3(NT), 0, (hipStream_t)stream, x, y, d, op);
+    });
 }
 
 // the rules every entry point holds a descriptor to; sets the error itself
@@ -146,152 +217,25 @@ int check_group_desc(const nlc_group_desc& d, const char* name) {
     return NLC_OK;
 }
 
-template <int OP>
-int launch_group(float* x, float* y, const nlc_group_desc& d, void* stream, const char* name) {
+template <class Op> int run_group(float* x, float* y, const nlc_group_desc& d, void* stream, const char* name) {
     NLC_REQUIRE(x && y, "%s: null pointer", name);
     NLC_TRY(check_group_desc(d, name));
-    hipStream_t s = (hipStream_t)stream;
-    if (d.mode == NLC_GROUP_CHANNEL) {
-        int g = cdiv((int64_t)d.H * d.W, NT); if (g > 1024) g = 1024;
-        hipLaunchKernelGGL((group_channel_kernel<OP>), dim3(g, d.B), dim3(NT), 0, s, x, y, d);
-    } else {
-        int g = cdiv((int64_t)d.C * (d.H / d.r) * (d.W / d.r), NT); if (g > 1024) g = 1024;
-        const dim3 grid(g, d.B);
-        switch (d.r) {
-            case 1: launch_block<1, OP>(x, y, d, grid, s); break;
-            case 2: launch_block<2, OP>(x, y, d, grid, s); break;
-            case 3: launch_block<3, OP>(x, y, d, grid, s); break;
-            case 4: launch_block<4, OP>(x, y, d, grid, s); break;
-            case 5: launch_block<5, OP>(x, y, d, grid, s); break;
-            case 6: launch_block<6, OP>(x, y, d, grid, s); break;
-            case 7: launch_block<7, OP>(x, y, d, grid, s); break;
-            default: launch_block<8, OP>(x, y, d, grid, s); break;
-        }
-    }
+    launch_group(x, y, d, Op{}, stream);
     NLC_CHECK_LAUNCH(name);
     return NLC_OK;
-}
-
-// ---- gradient-descent projection (gd.h).  v: the N entries of one group, yg its measurement.  GD_L2_SUM returns r^2 in double
-//      and leaves v alone; GD_L1 / GD_L2_APPLY update v (q: the sample's lr M_n / rho_0, l2 only). ------------------------------------
-template <int N, int PH>
-__device__ __forceinline__ double gd_group(float* v, float yg, const float* w, const gd_params& g, float q) {
-    const float r = __fsub_rn(group_sum<N>(w, v), yg);
-    if constexpr (PH == GD_L2_SUM) {
-        return (double)r * (double)r;
-    } else {
-        // x_i <- x_i - w_i a:  a = lr m_n (l1) or q r_g (l2), rounded once; the update is one fused multiply-add
-        const float a = PH == GD_L1 ? __fmul_rn(g.lr, gd_l1_steps(r, g.c, g.n_iter)) : __fmul_rn(q, r);
-#pragma unroll
-        for (int i = 0; i < N; ++i) v[i] = __fmaf_rn(-w[i], a, v[i]);
-        return 0.0;
-    }
-}
-
-template <int R, bool VEC, int PH>
-__global__ __launch_bounds__(NT) void group_block_gd_kernel(float* x, const float* y, const nlc_group_desc d, const gd_params g) {
-    __shared__ double sh[NT / 64];
-    const int Wb = d.W / R;
-    const int64_t G = (int64_t)d.C * (d.H / R) * Wb;
-    const int b = blockIdx.y;
-    float* xb = x + (int64_t)b * d.C * d.H * d.W;
-    const float* yb = y + (int64_t)b * G;
-    double* parts = g.partials + (int64_t)b * gridDim.x;
-    float q = 0.f;
-    if constexpr (PH == GD_L2_APPLY) {
-        q = gd_l2_scale(parts, gridDim.x, g, sh);
-        if (q == 0.f) return;                                               // rho_0 = 0 or M_n = 0: the sample stays as it is
-    }
-    double acc = 0.0;
-    for (int64_t gi = (int64_t)blockIdx.x * NT + threadIdx.x; gi < G; gi += (int64_t)gridDim.x * NT) {
-        const int64_t row = gi / Wb;
-        const int bx = (int)(gi - row * Wb);
-        float* base = xb + row * R * d.W + (int64_t)bx * R;
-        float v[R * R];
-#pragma unroll
-        for (int j = 0; j < R; ++j) load_row<R, VEC>(base + (int64_t)j * d.W, v + j * R);
-        acc += gd_group<R * R, PH>(v, yb[gi], d.w, g, q);
-        if constexpr (PH != GD_L2_SUM) {
-#pragma unroll
-            for (int j = 0; j < R; ++j) store_row<R, VEC>(base + (int64_t)j * d.W, v + j * R);
-        }
-    }
-    if constexpr (PH == GD_L2_SUM) {
-        acc = gd_block_sum(acc, sh);
-        if (threadIdx.x == 0) parts[blockIdx.x] = acc;
-    }
-}
-
-template <int PH>
-__global__ __launch_bounds__(NT) void group_channel_gd_kernel(float* x, const float* y, const nlc_group_desc d, const gd_params g) {
-    __shared__ double sh[NT / 64];
-    const int64_t HW = (int64_t)d.H * d.W;
-    const int b = blockIdx.y;
-    float* xb = x + (int64_t)b * 3 * HW;
-    const float* yb = y + (int64_t)b * HW;
-    double* parts = g.partials + (int64_t)b * gridDim.x;
-    float q = 0.f;
-    if constexpr (PH == GD_L2_APPLY) {
-        q = gd_l2_scale(parts, gridDim.x, g, sh);
-        if (q == 0.f) return;
-    }
-    double acc = 0.0;
-    for (int64_t p = (int64_t)blockIdx.x * NT + threadIdx.x; p < HW; p += (int64_t)gridDim.x * NT) {
-        float v[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) v[c] = xb[c * HW + p];
-        acc += gd_group<3, PH>(v, yb[p], d.w, g, q);
-        if constexpr (PH != GD_L2_SUM) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) xb[c * HW + p] = v[c];
-        }
-    }
-    if constexpr (PH == GD_L2_SUM) {
-        acc = gd_block_sum(acc, sh);
-        if (threadIdx.x == 0) parts[blockIdx.x] = acc;
-    }
-}
-
-template <int R, int PH>
-void launch_block_gd(float* x, const float* y, const nlc_group_desc& d, const gd_params& g, dim3 grid, hipStream_t s) {
-    constexpr bool kCanVec = R == 2 || R == 4 || R == 8;                    // as launch_block
-    const uintptr_t align = R == 2 ? 8 : 16;
-    if (kCanVec && ((uintptr_t)x % align) == 0)
-        hipLaunchKernelGGL((group_block_gd_kernel<R, kCanVec, PH>), grid, dim3(NT), 0, s, x, y, d, g);
-    else
-        hipLaunchKernelGGL((group_block_gd_kernel<R, false, PH>), grid, dim3(NT), 0, s, x, y, d, g);
-}
-
-template <int PH>
-void launch_gd(float* x, const float* y, const nlc_group_desc& d, const gd_params& g, hipStream_t s) {
-    if (d.mode == NLC_GROUP_CHANNEL) {
-        hipLaunchKernelGGL((group_channel_gd_kernel<PH>), dim3(gd_grid((int64_t)d.H * d.W), d.B), dim3(NT), 0, s, x, y, d, g);
-        return;
-    }
-    const dim3 grid(gd_grid((int64_t)d.C * (d.H / d.r) * (d.W / d.r)), d.B);
-    switch (d.r) {
-        case 1: launch_block_gd<1, PH>(x, y, d, g, grid, s); break;
-        case 2: launch_block_gd<2, PH>(x, y, d, g, grid, s); break;
-        case 3: launch_block_gd<3, PH>(x, y, d, g, grid, s); break;
-        case 4: launch_block_gd<4, PH>(x, y, d, g, grid, s); break;
-        case 5: launch_block_gd<5, PH>(x, y, d, g, grid, s); break;
-        case 6: launch_block_gd<6, PH>(x, y, d, g, grid, s); break;
-        case 7: launch_block_gd<7, PH>(x, y, d, g, grid, s); break;
-        default: launch_block_gd<8, PH>(x, y, d, g, grid, s); break;
-    }
 }
 }  // namespace
 
 extern "C" int nlc_group_A(const float* x, nlc_group_desc desc, float* y_out, void* stream) {
-    return launch_group<OP_A>(const_cast<float*>(x), y_out, desc, stream, "nlc_group_A");
+    return run_group<OpA>(const_cast<float*>(x), y_out, desc, stream, "nlc_group_A");
 }
 
 extern "C" int nlc_group_Apinv(const float* y, nlc_group_desc desc, float* x_out, void* stream) {
-    return launch_group<OP_APINV>(x_out, const_cast<float*>(y), desc, stream, "nlc_group_Apinv");
+    return run_group<OpApinv>(x_out, const_cast<float*>(y), desc, stream, "nlc_group_Apinv");
 }
 
 extern "C" int nlc_group_project(float* x0, const float* y, nlc_group_desc desc, void* stream) {
-    return launch_group<OP_PROJECT>(x0, const_cast<float*>(y), desc, stream, "nlc_group_project");
+    return run_group<OpProject>(x0, const_cast<float*>(y), desc, stream, "nlc_group_project");
 }
 
 extern "C" int64_t nlc_gd_workspace_bytes(int B, int64_t entries_per_sample) {
@@ -301,7 +245,6 @@ extern "C" int64_t nlc_gd_workspace_bytes(int B, int64_t entries_per_sample) {
 
 extern "C" int nlc_group_gd(float* x0, const float* y, nlc_group_desc desc, float lr, int n_iter, int loss, void* workspace,
                             void* stream) {
-    static_assert(NT == GD_NT, "the GD helpers reduce over GD_NT threads");
     const char* name = "nlc_group_gd";
     NLC_REQUIRE(x0 && y, "%s: null pointer", name);
     NLC_TRY(check_group_desc(desc, name));
@@ -313,14 +256,5 @@ extern "C" int nlc_group_gd(float* x0, const float* y, nlc_group_desc desc, floa
     NLC_REQUIRE(std::isfinite(lr * (float)n_iter) && std::isfinite((float)((double)lr * s2)),
                 "%s: lr * n_iter or lr * sum w^2 overflows float (lr = %g)", name, (double)lr);
     gd_params g{lr, (float)((double)lr * s2), (double)lr * s2, n_iter, (double*)workspace};
-    hipStream_t s = (hipStream_t)stream;
-    if (loss == 1) {
-        launch_gd<GD_L1>(x0, y, desc, g, s);
-    } else {
-        launch_gd<GD_L2_SUM>(x0, y, desc, g, s);
-        NLC_CHECK_LAUNCH(name);
-        launch_gd<GD_L2_APPLY>(x0, y, desc, g, s);
-    }
-    NLC_CHECK_LAUNCH(name);
-    return NLC_OK;
+    return gd_run(name, loss, [&](auto ph) { launch_group(x0, const_cast<float*>(y), desc, OpGd<ph()>{g}, stream); });
 }

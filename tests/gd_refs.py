@@ -33,7 +33,7 @@ import math
 import torch
 
 from tests import restore_refs as R
-from tests.restore_refs import A64, FIXTURE_CASES, LARGE_CASES, U32, bound_A, from_groups, inputs, tables  # noqa: F401
+from tests.restore_refs import A64, CLOSED_FORM_CASES, FIXTURE_CASES, LARGE_CASES, U32, bound_A, from_groups, inputs, tables  # noqa: F401
 
 INPAINT = "inpaint"
 N_ITER = 10
@@ -188,4 +188,4 @@ def gd_name(mode, C, dim, r, lr, loss):
 
 
 # every (case, lr, loss) the GPU op tests run
-OP_RUNS = [(c, lr, loss) for c in FIXTURE_CASES + LARGE_CASES for lr in LRS for loss in LOSSES]
+OP_RUNS = [(c, lr, loss) for c in FIXTURE_CASES + LARGE_CASES + CLOSED_FORM_CASES for lr in LRS for loss in LOSSES]

@@ -33,6 +33,9 @@ FIXTURE_CASES = [
 # float64 closed form only.  More groups per sample than one grid of 1024 x 256 threads, so the grid-stride loop wraps: 270 000
 # blocks, 270 400 pixels; 300 x 300 pixels fill 352 workgroups without wrapping
 LARGE_CASES = [(BLOCK, 3, 600, 2), (CHANNEL, 3, 300, 1), (CHANNEL, 3, 520, 1)]
+# float64 closed form only.  r = 5, 6, 7, the block sizes no fixture has: 2 x 2 blocks per channel, the smallest shape at which the
+# row and bx indexing of those instantiations can go wrong
+CLOSED_FORM_CASES = [(BLOCK, 3, 10, 5), (BLOCK, 3, 12, 6), (BLOCK, 3, 14, 7)]
 
 
 def case_name(mode, C, dim, r):

@@ -1,5 +1,5 @@
 """The gradient-descent projection kernels (csrc/restore.hip: nlc_group_gd; csrc/constraint.hip: nlc_inpaint_gd) through the public
-classes, at the shapes of tests/test_restore_ops_gpu.py - every row-load path, the r = 3 scalar rows, the grid-stride wrap - with
+classes, at the shapes of tests/test_restore_ops_gpu.py - every row-load path, the r = 3, 5, 6, 7 scalar rows, the grid-stride wrap - with
 n_iter = 10, lr in {10, 0.5}, both losses and B = 2 (a batch-wide norm in place of the per-sample one would show).
 
 Every output is held to the ITERATED float64 form of tests/gd_refs.py within bound_gd, outside the guard (both derived there; the

@@ -5,6 +5,7 @@ classes ``SuperResolution`` and ``Colorization``, at the smallest shapes at whic
              (3, 6, 2) (3, 12, 4)              odd number of blocks per row
              (3, 12, 3) (1, 9, 3)              r = 3: scalar path, unaligned rows
              (3, 16, 1)                        r = 1: A is the identity, bit exact
+             (3, 10, 5) (3, 12, 6) (3, 14, 7)  r = 5, 6, 7: 2 x 2 blocks per channel, float64 closed form only
              (3, 600, 2)                       270 000 groups > 1024 x 256 threads: the grid-stride loop wraps
     CHANNEL  img_dim 1, 8, 300, 520            single pixel; plane-strided reads; many workgroups; 270 400 pixels: the loop wraps
 
@@ -113,6 +114,12 @@ def test_group_ops_small(mode, C, dim, r):
 def test_group_ops_grid_stride_wrap(mode, C, dim, r):
     x, x0 = R.inputs(mode, C, dim, r)
     assert R.A64(x, mode, r).shape[1] > (256 if dim == 300 else 1024 * 256)
+    check_case(make_op(mode, C, dim, r), mode, C, dim, r, x, x0, R.A64(x, mode, r).float(), issue_bound=False)
+
+
+@pytest.mark.parametrize("mode,C,dim,r", R.CLOSED_FORM_CASES, ids=[R.case_name(*c) for c in R.CLOSED_FORM_CASES])
+def test_group_ops_block_sizes_without_a_fixture(mode, C, dim, r):
+    x, x0 = R.inputs(mode, C, dim, r)
     check_case(make_op(mode, C, dim, r), mode, C, dim, r, x, x0, R.A64(x, mode, r).float(), issue_bound=False)
 
 
